@@ -7,7 +7,24 @@ region (resident in HBM).  One step = demap + sum-product BP (+ error
 counting) over the whole resident batch, i.e. KmCodec::Decoder + SourceSink::CntErr
 (src/kmcodec.cc:54-72, lib/lab/src/sourcesink.cc:29-47) for B codewords.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--blind]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--blind] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with
+the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and
+the run's shape; nothing else touches the GPU or the host cores.
+
+--dump-outputs DIR writes the results of the last timed step as DIR/<name>.npy:
+cw_err.npy (float32, the error bits of every codeword of the batch) and
+counters.npy (float64: err_bit, err_blk, tot_bit, tot_blk, vn_phases,
+cn_phases, converged, redone).  The timed calls (kml_sim_decode, no sync) hand
+nothing back, so after the timed region the step is issued once more through
+kml_sim_decode_ex: the same launches on the same resident frames plus the
+copy-out, and the decode is deterministic.  The timed region is the same with
+and without the option.  The frames depend on the arguments only (Philox,
+--seed), so two builds can be compared array by array.  Rank r > 0 of a
+multi-rank run writes <name>_rank<r>.npy.
+
+--full adds everything described under "Besides the timed region" below.
 
 --gpus N > 1 without a torch.distributed environment starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
@@ -18,7 +35,11 @@ collective) and the error counters are summed with one RCCL all-reduce at the
 end (simulator.cc:35-42, :86-100 run SNR points / codeword chunks as
 independent tasks the same way).  Rank 0 prints ONE JSON line.
 
-Besides the timed region the line carries, all untimed:
+Besides the timed region the line carries with --full, all untimed:
+  * stats: FER / BER / BP phase counters of one more decode of the timed batch,
+    summed over the ranks (RCCL all-reduce), and roofline: the BP kernel's
+    launch times inside the timed region against the fp64 peak, with the PMC
+    map entry of the workload (profiles/pmc_bp.json);
   * stats.ber_match: the first B_ref codewords of the reference's own seed-17
     stream (CLCRandNum::SetSeed(-1)) decoded on the GPU, compared codeword by
     codeword with the reference's SourceSink::CntErr counters for the same
@@ -280,6 +301,83 @@ def ber_sigma(sum_e, sum_e2, n, Kbits):
     return math.sqrt(var / n) / Kbits
 
 
+def gather_times(dist, ranks_seen, elapsed, fl_t):
+    """Every rank's timed-region seconds, and the slowest rank's full-loop
+    seconds (gloo all_gather: the CPU control channel)."""
+    if dist is None:
+        return [elapsed], fl_t
+    import torch
+
+    tt = torch.tensor([elapsed, fl_t], dtype=torch.float64)
+    gathered = [torch.zeros_like(tt) for _ in range(ranks_seen)]
+    dist.all_gather(gathered, tt)
+    return [float(g[0].item()) for g in gathered], max(float(g[1].item()) for g in gathered)
+
+
+def headline(args, world, B, per_rank, dist, comm_ranks, ranks_seen):
+    """The result line of a plain run: the timed region and the run's shape."""
+    t_max = max(per_rank)
+    if dist is None:
+        backend = None
+    elif args.full:
+        backend = ("rccl" if comm_ranks else "gloo") + " counters, gloo control"
+    else:
+        backend = "gloo control"
+    return {
+        "metric": "decoded codewords/sec (N=2304 R=1/2, 20 BP iters) at 1/2/4/8 GPUs; BER match",
+        "value": round(B * args.steps * world / t_max, 1),
+        "unit": "codewords/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(t_max / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic y=h*x+w frames generated on the GPU (Philox), resident in HBM before timing",
+        "full": bool(args.full),
+        "config": {
+            "workload": f"{args.matrix.split('.txt')[0]} + {args.modem.split('.txt')[0]}, Es/N0 {args.snr} dB, "
+                        f"max {args.max_iter} BP iters, {'blind k-means' if args.blind else 'known-H ideal'} demap",
+            "batch_per_gpu": B,
+            "global_batch": B * world,
+            "parallelism": f"codeword-sharded x{world}",
+        },
+        "dist_backend": backend,
+        # ranks of the library's RCCL communicator (0: none — one process, gloo counters, or a plain run)
+        "rccl_ranks": comm_ranks,
+        "ranks": ranks_seen,
+        "rank_ms_per_step": [round(t / args.steps * 1e3, 3) for t in per_rank],
+    }
+
+
+def dump_outputs(out_dir, rank, cw_err, counters):
+    """The timed step's results, as float arrays (both exact: the
+    error bits of a codeword are below 2^24, the counters far below 2^53)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    keys = ("err_bit", "err_blk", "tot_bit", "tot_blk", "vn_phases", "cn_phases", "converged", "redone")
+    np.save(os.path.join(out_dir, f"cw_err{tag}.npy"), cw_err.astype(np.float32))
+    np.save(os.path.join(out_dir, f"counters{tag}.npy"), np.array([counters[k] for k in keys], dtype=np.float64))
+
+
+def finish(ctx, dist):
+    ctx.close()  # release the device buffers while the runtime is fully up
+    if os.environ.get("KML_DUMP_MAPS"):  # diagnostics: map a crash at exit to its library
+        with open("/proc/self/maps") as src, open(os.environ["KML_DUMP_MAPS"], "w") as dst:
+            dst.write(src.read())
+    if os.environ.get("KML_EXIT_RESET") == "1":  # diagnostics: tear the device down before exit()
+        import ctypes
+        hip = ctypes.CDLL("libamdhip64.so")  # the library's runtime (torch's is never started here)
+        print("hipDeviceSynchronize:", hip.hipDeviceSynchronize(), "hipDeviceReset:", hip.hipDeviceReset(),
+              file=sys.stderr, flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -303,10 +401,17 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="run under torch.distributed.run and build the process group (init, all_reduce, "
                          "all_gather) even for --gpus 1: a 1-rank RCCL group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the timed step (cw_err, counters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs: stats and roofline, full loop, BER match against the "
+                         "reference stream, CPU baseline, and the RCCL all-reduce of the counters")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (RCCL over xGMI, the production path) or gloo (CPU counters; lets N ranks share "
                          "fewer GPUs for testing)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -346,7 +451,7 @@ def main():
     cfg = write_config(d, args)
     ctx = K.Context(cfg, data_dir=d, device=device)
     comm_ranks = 0
-    if dist is not None and args.dist_backend == "nccl":
+    if args.full and dist is not None and args.dist_backend == "nccl":
         uid = [K.comm_unique_id() if rank == 0 else None]
         dist.broadcast_object_list(uid, src=0)
         ctx.comm_init(uid[0], ranks_seen, rank)  # RCCL communicator over the ranks' GPUs (xGMI)
@@ -372,6 +477,18 @@ def main():
     t1 = time.perf_counter()
     ctx.prof_enable(False)
     elapsed = t1 - t0
+    if args.dump_outputs:
+        # The timed calls hand nothing back (no copy-out inside the timed region).  The last step's results are
+        # read by issuing that step once more, untimed, through the call that returns them: the same launches on
+        # the same resident frames, and the decode is deterministic, so these are the arrays that step computed.
+        last_err, _, last_cnt = ctx.sim_decode_ex(args.snr, blind=args.blind)
+        dump_outputs(args.dump_outputs, rank, last_err, last_cnt)
+    if not args.full:
+        per_rank, _ = gather_times(dist, ranks_seen, elapsed, 0.0)
+        if rank == 0:
+            print(json.dumps(headline(args, world, B, per_rank, dist, comm_ranks, ranks_seen)), flush=True)
+        finish(ctx, dist)
+        return
     bp = ctx.prof_read("bp")
     bp_kernel = ctx.bp_kernel()
     stages = {s: ctx.prof_read(s) for s in ("demap", "kmeans", "metric")}
@@ -393,7 +510,7 @@ def main():
         barrier()
         fl_t = time.perf_counter() - tf
 
-    t_max, fl_max, per_rank = elapsed, fl_t, [elapsed]
+    fl_max, per_rank = fl_t, [elapsed]
     if dist is not None:
         import torch
         if comm_ranks:
@@ -402,19 +519,12 @@ def main():
             tv = torch.tensor(vals)
             dist.all_reduce(tv)  # gloo (CPU counters)
             vals = tv.numpy()
-        tt = torch.tensor([elapsed, fl_t], dtype=torch.float64)
-        gathered = [torch.zeros_like(tt) for _ in range(ranks_seen)]
-        dist.all_gather(gathered, tt)  # timing: CPU control channel
-        per_rank = [float(g[0].item()) for g in gathered]
-        t_max = max(per_rank)
-        fl_max = max(float(g[1].item()) for g in gathered)
+        per_rank, fl_max = gather_times(dist, ranks_seen, elapsed, fl_t)
 
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
         return
-    total_cw = B * args.steps * world
-    value = total_cw / t_max
     err_bit, err_blk, tot_bit, tot_blk, vn, cn, sum_e, sum_e2, redone = vals
     Kbits = tot_bit / max(tot_blk, 1)
     bp_avg_ms = bp["ms"] / max(bp["launches"], 1)
@@ -509,31 +619,8 @@ def main():
                 "exact": same and ref_bit == int(gc["err_bit"]) and ref_blk == int(gc["err_blk"]),
             },
         })
-    line = {
-        "metric": "decoded codewords/sec (N=2304 R=1/2, 20 BP iters) at 1/2/4/8 GPUs; BER match",
-        "value": round(value, 1),
-        "unit": "codewords/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(t_max / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic y=h*x+w frames generated on the GPU (Philox), resident in HBM before timing",
-        "config": {
-            "workload": f"{args.matrix.split('.txt')[0]} + {args.modem.split('.txt')[0]}, Es/N0 {args.snr} dB, "
-                        f"max {args.max_iter} BP iters, {'blind k-means' if args.blind else 'known-H ideal'} demap",
-            "batch_per_gpu": B,
-            "global_batch": B * world,
-            "parallelism": f"codeword-sharded x{world}",
-        },
-        "dist_backend": (("rccl" if comm_ranks else "gloo") + " counters, gloo control") if dist is not None else None,
-        # ranks of the library's RCCL communicator (0: none — one process, or gloo counters)
-        "rccl_ranks": comm_ranks,
-        "ranks": ranks_seen,
-        "rank_ms_per_step": [round(t / args.steps * 1e3, 3) for t in per_rank],
+    line = headline(args, world, B, per_rank, dist, comm_ranks, ranks_seen)
+    line.update({
         "full_loop": {
             "value": round(fl_n * B * world / fl_max, 1) if fl_max > 0 else None,
             "unit": "codewords/s",
@@ -577,21 +664,11 @@ def main():
             },
         },
         "stats": stats,
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(d, args)
     print(json.dumps(line), flush=True)
-    ctx.close()  # release the device buffers while the runtime is fully up
-    if os.environ.get("KML_DUMP_MAPS"):  # diagnostics: map a crash at exit to its library
-        with open("/proc/self/maps") as src, open(os.environ["KML_DUMP_MAPS"], "w") as dst:
-            dst.write(src.read())
-    if os.environ.get("KML_EXIT_RESET") == "1":  # diagnostics (W3): tear the device down before exit()
-        import ctypes
-        hip = ctypes.CDLL("libamdhip64.so")  # the library's runtime (torch's is never started here)
-        print("hipDeviceSynchronize:", hip.hipDeviceSynchronize(), "hipDeviceReset:", hip.hipDeviceReset(),
-              file=sys.stderr, flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    finish(ctx, dist)
 
 
 if __name__ == "__main__":

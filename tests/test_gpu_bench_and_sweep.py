@@ -156,7 +156,7 @@ def test_bench_two_ranks_gloo(data_dir, tmp_path):
     decode of the whole index range."""
     B = 2048
     line = _bench(["--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", str(B),
-                   "--no-cpu-baseline", "--no-ber-match", "--full-loop-batches", "1"])
+                   "--full", "--no-cpu-baseline", "--no-ber-match", "--full-loop-batches", "1"])
     assert line["n_gpus"] == 2 and line["ranks"] == 2 and line["dist_backend"].startswith("gloo counters")
     assert len(line["rank_ms_per_step"]) == 2 and line["config"]["global_batch"] == 2 * B
     st = line["stats"]
@@ -179,7 +179,7 @@ def test_bench_eight_ranks_gloo(data_dir, tmp_path):
     one decode of the whole index range [0, 8 B) (simulator.cc:35-42, 86-100)."""
     B, W = 512, 8
     line = _bench(["--gpus", str(W), "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", str(B),
-                   "--no-cpu-baseline", "--no-ber-match", "--full-loop-batches", "1"], timeout=380)
+                   "--full", "--no-cpu-baseline", "--no-ber-match", "--full-loop-batches", "1"], timeout=380)
     assert line["n_gpus"] == W and line["ranks"] == W and line["dist_backend"].startswith("gloo counters")
     assert len(line["rank_ms_per_step"]) == W and line["config"]["global_batch"] == W * B
     assert line["ms_per_step"] == pytest.approx(max(line["rank_ms_per_step"]), rel=1e-6)
@@ -223,7 +223,7 @@ def test_bench_one_rank_rccl_group(data_dir):
     communicator (kml_comm_unique_id / kml_comm_init) and all-reduces the
     counters through it (kml_comm_allreduce_f64, on the context's stream); its
     counters equal the plain single-process run on the same frames."""
-    args = ["--steps", "2", "--warmup", "1", "--batch", "2048", "--no-cpu-baseline", "--no-ber-match",
+    args = ["--full", "--steps", "2", "--warmup", "1", "--batch", "2048", "--no-cpu-baseline", "--no-ber-match",
             "--full-loop-batches", "1"]
     plain = _bench(args)
     line = _bench(args + ["--gpus", "1", "--force-dist"])
@@ -257,13 +257,42 @@ def test_simulate_one_rank_rccl_group(data_dir, tmp_path):
 def test_bench_single_rank_line(data_dir):
     """The N=1 line carries the roofline (fp64-valu), the exact BER match on
     the reference stream and the 1-sigma statistic."""
-    line = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full-loop-batches", "1"])
+    line = _bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full-loop-batches", "1"])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 0 and line["dist_backend"] is None
     rf = line["roofline"]
     assert rf["bound"] == "fp64-valu" and 0 < rf["frac"] < 1
     bm = line["stats"]["ber_match"]
     assert bm["exact"] and bm["per_codeword_equal"]
     assert isinstance(line["stats"]["ber_within_1sigma"], bool)
+
+
+def test_bench_plain_run_is_lean_and_dumps_last_step(data_dir, tmp_path):
+    """A plain run prints the headline only (none of the --full legs), its
+    value and ms_per_step describe the same --steps timed steps, and
+    --dump-outputs writes the timed step's results: float arrays equal to a
+    decode of the same Philox frames (seed 17, codewords [0, B)) here."""
+    B = 2048
+    out = tmp_path / "dump"
+    line = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--dump-outputs", str(out)])
+    for k in ("stats", "full_loop", "roofline", "cpu_baseline"):
+        assert k not in line, k
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "codewords/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0
+    # value is rounded to 0.1 and ms_per_step to 0.001 in the line
+    assert line["value"] == pytest.approx(B / (line["ms_per_step"] * 1e-3), rel=0.001 / line["ms_per_step"] + 1e-6)
+    assert sorted(os.listdir(out)) == ["counters.npy", "cw_err.npy"]
+    cw = np.load(out / "cw_err.npy")
+    cnt = np.load(out / "counters.npy")
+    assert cw.dtype == np.float32 and cw.shape == (B,) and cnt.dtype == np.float64 and cnt.shape == (8,)
+    ctx = _ctx(data_dir, tmp_path, "PEG2304regular0.5.txt", "2bits_QPSK.txt")
+    ctx.sim_generate(2.0, B, seed=17, first_cw=0)
+    cw_err, _, c = ctx.sim_decode_ex(2.0, blind=False)
+    ctx.close()
+    assert np.array_equal(cw, cw_err.astype(np.float32))
+    assert [int(v) for v in cnt] == [c[k] for k in ("err_bit", "err_blk", "tot_bit", "tot_blk", "vn_phases",
+                                                    "cn_phases", "converged", "redone")]
+    assert cnt[0] == cw.sum() and cnt[1] == (cw > 0).sum() and cnt[3] == B
 
 
 CFG5_SNRS = [4.77, 5.77, 6.77, 7.77, 8.77]

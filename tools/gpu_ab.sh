@@ -29,7 +29,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
       l=${spec%%:*}; LE=""; tag=$l
       case $spec in *:*) LE=${spec#*:}; tag=${l}_$(echo ${LE#KML_} | tr '=' '_');; esac
       if [ "$l" = main ]; then L=kmldpc_amd/libkmldpc_amd.so; else L=kmldpc_amd/libkmldpc_amd_$l.so; fi
-      env $E $LE KML_LIB=$L timeout -k 10 200 python bench.py $A --no-cpu-baseline --no-ber-match --full-loop-batches 0 > $O/${w}_${tag}_$r.json 2> $O/${w}_${tag}_$r.err || exit $?
+      env $E $LE KML_LIB=$L timeout -k 10 200 python bench.py --full $A --no-cpu-baseline --no-ber-match --full-loop-batches 0 > $O/${w}_${tag}_$r.json 2> $O/${w}_${tag}_$r.err || exit $?
       python3 -c "import json,sys; d=json.loads(open('$O/${w}_${tag}_$r.json').read().strip().splitlines()[-1]); print('$w $tag $r', d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'], d['stats'].get('stage_ms_per_step'), 'redone', d['stats'].get('redone'))" >> $O/summary.txt
     done
   done

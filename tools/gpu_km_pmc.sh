@@ -6,7 +6,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-kmpmc}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-P="--blind --steps 2 --warmup 1 --no-cpu-baseline --no-ber-match --full-loop-batches 0"
+P="--full --blind --steps 2 --warmup 1 --no-cpu-baseline --no-ber-match --full-loop-batches 0"
 for spec in main ${2:+alt:$2}; do
   tag=${spec%%:*}; E=""; case $spec in *:*) E=${spec#*:};; esac
   [ -n "$E" ] && export $E

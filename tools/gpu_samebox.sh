@@ -11,8 +11,8 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name, coop env, bench args...
   local n=$1 env=$2; shift 2
   echo "== $n $(date +%T)" >> $O/steps.log
-  timeout -k 10 300 python3 $R/bench.py "$@" > $O/$n.json 2> $O/$n.err || return $?
-  env $env timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/t_$n -o run --output-format csv -- python3 $R/bench.py "$@" > $O/$n.traced.json 2> $O/$n.traced.log || return $?
+  timeout -k 10 300 python3 $R/bench.py --full "$@" > $O/$n.json 2> $O/$n.err || return $?
+  env $env timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/t_$n -o run --output-format csv -- python3 $R/bench.py --full "$@" > $O/$n.traced.json 2> $O/$n.traced.log || return $?
 }
 run headline KML_COOP_LAUNCH=1 || exit $?
 run blind KML_COOP_LAUNCH=1 --blind || exit $?

@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/pmc_$NAME
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-P="--steps 2 --warmup 1 --no-cpu-baseline --no-ber-match --full-loop-batches 0 $*"
+P="--full --steps 2 --warmup 1 --no-cpu-baseline --no-ber-match --full-loop-batches 0 $*"
 step() { echo "== $NAME $1 $(date +%T)" >> $R/gpurun_out/pmc_steps.log; }
 # PASSES selects passes (default all).  A process that made a cooperative launch
 # under rocprofv3 crashes in the ROCm runtime's exit-time teardown after the
