@@ -107,6 +107,32 @@ int kml_abi_version(void);
  * PEG8064), "bp_kernel"; "" before any decode). */
 const char *kml_bp_kernel(const kml_ctx *ctx);
 
+/* Arithmetic of the BP decoder, per context.  KML_PREC_F64 (the default) is the
+ * bit-exact restatement of the reference.  KML_PREC_F32 is an opt-in
+ * single-precision decoder for Monte-Carlo BER / FER work ("bp_regular_f32_kernel"
+ * in kml_bp_kernel): the same schedule, stop rule and return value with float
+ * messages and hardware reciprocals.  It is NOT bit-exact with the reference
+ * and promises no particular bit of uu_hat, ret, cc_hat or syn.  What it does
+ * guarantee, and the test suite checks against the reference arithmetic on
+ * seed-17 streams (QPSK at 2 dB, 16QAM at 8 dB, 64QAM at 13 dB): at most 2 % of
+ * the codewords differ in uu_hat, in ret or in cc_hat; a call's results do not
+ * depend on the batch size or on the codeword's place in the batch and repeat
+ * from call to call; the fused and the separate demap paths agree bit for bit
+ * within the mode.  The mode changes the final BP decode of kml_bp_decode,
+ * kml_decode_frames, kml_decode_candidates, kml_sim_decode(_ex) and
+ * kml_sim_point only: the demapper, k-means and the candidate metrics (chosen,
+ * metrics, h_hat) stay fp64 and unchanged, and syn is still double (float
+ * values widened).  The soft-syndrome metric (metric_type = 1), whose
+ * candidates' metrics depend on earlier final decodes, returns KML_E_UNSUP
+ * in the f32 mode.
+ * kml_set_precision returns KML_E_UNSUP, and leaves the context in fp64, when
+ * the context's code does not take the f32 kernel (only PEG2304-class codes do:
+ * regular, dv 3, dc 6, N = 2304, M = 1152) or the context is host-only, and
+ * KML_E_ARG for an unknown value.  There is no fallback in either direction. */
+enum { KML_PREC_F64 = 0, KML_PREC_F32 = 1 };
+int kml_set_precision(kml_ctx *ctx, int prec);
+int kml_get_precision(const kml_ctx *ctx);
+
 int kml_dims(const kml_ctx *ctx, int32_t *dims /* [KML_DIM_COUNT] */);
 /* Host-side code plan, for inspection and parity tests. */
 int kml_code_perm(const kml_ctx *ctx, int32_t *perm /* [Ncol] */);

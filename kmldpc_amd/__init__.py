@@ -30,6 +30,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include", "kmldpc_amd.h")
 
 KML_DEVICE_PTRS = 1
 KML_HISTOGRAM = 2
+PRECISIONS = {"f64": 0, "f32": 1}  # KML_PREC_F64, KML_PREC_F32
 DIM_NAMES = ["M", "Ncol", "K", "cc_len", "Z", "E", "chk", "max_iter", "bits", "Kc", "S", "bp_lds", "part_group"]
 
 
@@ -76,6 +77,8 @@ def lib():
     sig = {
         "kml_abi_version": (I, []),
         "kml_bp_kernel": (C.c_char_p, [P]),
+        "kml_set_precision": (I, [P, I]),
+        "kml_get_precision": (I, [P]),
         "kml_create": (I, [C.c_char_p, C.c_char_p, I, PP]),
         "kml_create_explicit": (I, [C.c_char_p, C.c_char_p, I, I, I, I, I, I, PP]),
         "kml_destroy": (None, [P]),
@@ -156,7 +159,7 @@ class Context:
     """One code + modem on one GPU (device < 0: host-only planner context)."""
 
     def __init__(self, config=None, data_dir=None, device=0, *, matrix_file=None, modem_file=None, is5g=False,
-                 active=True, max_iter=20, metric_soft=False, metric_iter=5):
+                 active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64"):
         L = lib()
         h = C.c_void_p()
         if config is not None:
@@ -181,6 +184,12 @@ class Context:
             setattr(self, k, v)
         self.device = device
         self._sim_B = 0
+        if precision != "f64":
+            try:
+                self.set_precision(precision)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -202,6 +211,20 @@ class Context:
     def _chk(self, r, what):
         if r != 0:
             raise KmlError(f"{what}: {lib().kml_last_error(self._h).decode()} (code {r})")
+
+    # ---- BP arithmetic (kml_set_precision)
+    def set_precision(self, precision):
+        """"f64" (default, bit-exact with the reference) or "f32" (opt-in single-precision BP
+        decode, PEG2304-class codes only, not bit-exact; raises KmlError with code -4 elsewhere)."""
+        if precision not in PRECISIONS:
+            # an unknown name reaches the library as an unknown value, which answers KML_E_ARG
+            self._chk(lib().kml_set_precision(self._h, -1), f"kml_set_precision({precision!r})")
+        self._chk(lib().kml_set_precision(self._h, PRECISIONS[precision]), f"kml_set_precision({precision!r})")
+
+    @property
+    def precision(self):
+        v = int(lib().kml_get_precision(self._h))
+        return {n: k for k, n in PRECISIONS.items()}[v]
 
     # ---- planner / host side
     def perm(self):

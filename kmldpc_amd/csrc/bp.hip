@@ -325,6 +325,19 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
     if (err) *err = "dequeue counter missing";
     return hipErrorInvalidValue;
   }
+  if (a.prec != 0) {  // the opt-in single-precision mode: its kernel or an error, never another family
+    if (a.prec != 1) {
+      if (err) *err = "unknown BP precision";
+      return hipErrorInvalidValue;
+    }
+    hipError_t e = launch_bp_regular_f32(c, a, s);
+    if (e == hipErrorNotSupported) {
+      if (err) *err = "the single-precision BP kernel does not take this code or launch";
+      return e;
+    }
+    if (family) *family = "bp_regular_f32_kernel";
+    return e;
+  }
   const bool lds = bp_uses_lds(c);
   // kernel families, most specialised first: regular PEG2304-class (LDS),
   // irregular with degrees <= 9 / 10 (LDS), cooperative regular (L2), generic

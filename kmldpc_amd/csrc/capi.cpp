@@ -68,6 +68,7 @@ constexpr int kArenaSlots = 1024;
 struct kml_ctx {
   int device = 0;
   const char *bp_family = nullptr;  // kernel family of the last BP launch
+  int precision = KML_PREC_F64;     // kml_set_precision: arithmetic of the final BP decodes
   hipStream_t stream = nullptr;
   hipStream_t cstream = nullptr;  // host-buffer frame uploads (kml_decode_frames' chunked path), made on first use
   kml::RunConfig rc;
@@ -420,7 +421,10 @@ void drain_profile(kml_ctx *c) {
 
 // Launch BP over n entries with a fresh counter slot; returns the slot.
 // reuse >= 0 accumulates into that (already zeroed) slot.
-int run_bp(kml_ctx *c, kml::BpLaunch a, int &slot_out, int reuse = -1) {
+// metric = true: a candidate-metric decode of the blind front end, which stays
+// fp64 in every mode (kml_set_precision changes the final decodes only).
+int run_bp(kml_ctx *c, kml::BpLaunch a, int &slot_out, int reuse = -1, bool metric = false) {
+  a.prec = metric ? KML_PREC_F64 : c->precision;
   const int slot = reuse >= 0 ? reuse : next_slot(c);
   if (reuse < 0)
     HIPCHK(c, hipMemsetAsync(slot_ptr(c, slot), 0, sizeof(unsigned long long) * kml::CNT_N, c->stream), "memset");
@@ -703,7 +707,7 @@ int receive(kml_ctx *c, const RecvIO &io, double snr, int B, int &bp_slot) {
     m.uu_hat = c->w_uh4.as<uint8_t>();
   }
   int mslot = 0;
-  TRY(run_bp(c, m, mslot));
+  TRY(run_bp(c, m, mslot, -1, true));
   HIPCHK(c, kml::launch_select(c->w_pc.as<int32_t>(), nc, B, met, chosen, c->stream), "select");
   if (io.histogram) {
     const uint8_t *last = c->w_uh4.as<uint8_t>() + (size_t)(nc - 1) * K;
@@ -740,6 +744,10 @@ int soft_receive(kml_ctx *c, const RecvIO &io, double var, int B, const double2 
   const size_t cc = (size_t)c->code.cc_len;
   const int K = c->code.K, M = c->code.M;
   const int mit = c->rc.metric_iter, max_iter = c->rc.max_iter;
+  // the walk below takes a final decode for a repeat of its candidate's metric
+  // decode and feeds its syndromes to the next codeword's metrics: one arithmetic
+  if (c->precision != KML_PREC_F64)
+    return fail(c, KML_E_UNSUP, "the soft-syndrome metric (metric_type = 1) is not available in the f32 mode");
   const double *cons = c->d_cons.as<double>();
   const size_t nB = (size_t)nc * B;
   HIPCHK(c, c->w_p0.ensure(sizeof(double) * cc * nB), "hipMalloc(p0)");
@@ -768,7 +776,7 @@ int soft_receive(kml_ctx *c, const RecvIO &io, double var, int B, const double2 
     m.uu_hat = c->w_uh4.as<uint8_t>();
   }
   int mslot = 0;
-  TRY(run_bp(c, m, mslot));
+  TRY(run_bp(c, m, mslot, -1, true));
   {
     Timer t(c, "metric", -1, (double)nB * M * 8.0);
     HIPCHK(c, kml::launch_soft_sum(m.syn, M, m.iters, nullptr, (int)nB, c->s_Lm.as<double>(), c->stream), "soft sum");
@@ -976,6 +984,25 @@ static thread_local std::string g_free_err = "null context";
 const char *kml_last_error(const kml_ctx *c) { return c ? c->err.c_str() : g_free_err.c_str(); }
 
 const char *kml_bp_kernel(const kml_ctx *c) { return c && c->bp_family ? c->bp_family : ""; }
+
+int kml_set_precision(kml_ctx *c, int prec) {
+  if (!c) return KML_E_ARG;
+  call_begin(c);
+  if (prec != KML_PREC_F64 && prec != KML_PREC_F32)
+    return fail(c, KML_E_ARG, "kml_set_precision: unknown precision " + std::to_string(prec));
+  if (prec == KML_PREC_F32) {
+    if (c->device < 0 || !c->stream)
+      return fail(c, KML_E_UNSUP, "kml_set_precision: a host-only context (device < 0) has no f32 decoder");
+    if (!kml::bp_regular_f32_supported(c->dc))
+      return fail(c, KML_E_UNSUP,
+                  "kml_set_precision: the f32 decoder takes only PEG2304-class codes (regular, dv 3, dc 6, N = 2304, "
+                  "M = 1152); the context stays in fp64");
+  }
+  c->precision = prec;
+  return KML_OK;
+}
+
+int kml_get_precision(const kml_ctx *c) { return c ? c->precision : KML_E_ARG; }
 
 int kml_dims(const kml_ctx *c, int32_t *d) {
   if (!c || !d) return KML_E_ARG;

@@ -98,6 +98,10 @@ struct BpLaunch {
   const double *sym_cons = nullptr;  // the normalised constellation, 2 << bits doubles
   double sym_var = 0;
   int sym_bits = 0;
+  // 0: the bit-exact fp64 kernels; 1: the single-precision kernel
+  // (bp_regular_f32.hip, PEG2304-class codes only; launch_bp fails for any
+  // other code, there is no fallback in either direction)
+  int prec = 0;
 };
 
 // FAST-path mode of a BP launch: bit 0 = FAST division allowed (column degree
@@ -108,6 +112,9 @@ int bp_fast_mode(const DevCode &c);
 hipError_t launch_bp_regular(const DevCode &c, const BpLaunch &a, hipStream_t s);
 // Can the regular kernel compute P0 itself (BpLaunch::sym_y) for this code and modem?
 bool bp_regular_fuses_demap(const DevCode &c, int bits);
+// The single-precision sibling (BpLaunch::prec = 1) and whether this code takes it.
+hipError_t launch_bp_regular_f32(const DevCode &c, const BpLaunch &a, hipStream_t s);
+bool bp_regular_f32_supported(const DevCode &c);
 hipError_t launch_bp_irregular(const DevCode &c, const BpLaunch &a, hipStream_t s);
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of
 // workgroups on one XCD share a codeword.  0 groups = not applicable.

@@ -15,7 +15,9 @@
 //
 // Environment: KML_DEVICE (GPU ordinal, default 0), KML_BATCH (codewords per
 // GPU round, default 32768), KML_SEED (frame seed, default 0 like
-// CLCRandNum::SetSeed(0) in kmldpc.cpp:22).
+// CLCRandNum::SetSeed(0) in kmldpc.cpp:22), KML_PRECISION (f64 or f32, also
+// `--precision f64|f32` on the command line: the BP decode arithmetic,
+// kml_set_precision; an f32 run states the mode in its first line).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -92,8 +94,22 @@ int main(int argc, char **argv) {
     const std::string name = "logs/" + now_string() + "-kmldpc.logger";
     g_log = fopen(name.c_str(), "w");
   }
+  std::string cfg = "config.toml", prec = getenv("KML_PRECISION") ? getenv("KML_PRECISION") : "f64";
+  for (int i = 1; i < argc; i++) {
+    const std::string arg = argv[i];
+    if (arg == "--precision" && i + 1 < argc)
+      prec = argv[++i];
+    else if (arg.rfind("--precision=", 0) == 0)
+      prec = arg.substr(12);
+    else
+      cfg = arg;
+  }
+  if (prec != "f64" && prec != "f32") {
+    error("--precision / KML_PRECISION must be f64 or f32");
+    return 255;
+  }
+  if (prec == "f32") info("BP decode precision: f32 (single precision, not bit-exact with the reference)");
   info("Start simulation");
-  const std::string cfg = argc > 1 ? argv[1] : "config.toml";
   {
     FILE *f = fopen(cfg.c_str(), "rb");
     if (!f) {
@@ -111,6 +127,11 @@ int main(int argc, char **argv) {
     error(ctx ? kml_last_error(ctx) : "kml_create failed");
     kml_destroy(ctx);
     return 255;  // the reference exits with -1 on setup errors
+  }
+  if (prec == "f32" && kml_set_precision(ctx, KML_PREC_F32) != KML_OK) {
+    error(kml_last_error(ctx));
+    kml_destroy(ctx);
+    return 255;
   }
   double f[3];
   int64_t n[10];

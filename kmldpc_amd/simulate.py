@@ -75,15 +75,17 @@ def point_seed(seed, i):
 class Simulator:
     """Simulator (include/simulator.h): constructed from config.toml, Simulate() runs the sweep."""
 
-    def __init__(self, config, data_dir=None, device=0, batch=32768, seed=0, dist=None, log=None, comm_backend="nccl"):
-        self.ctx = Context(config, data_dir=data_dir or os.path.dirname(os.path.abspath(config)), device=device)
+    def __init__(self, config, data_dir=None, device=0, batch=32768, seed=0, dist=None, log=None, comm_backend="nccl",
+                 precision="f64"):
+        self.log = log or Logger(enabled=(dist.get_rank() if dist else 0) == 0)
+        self.ctx = Context(config, data_dir=data_dir or os.path.dirname(os.path.abspath(config)), device=device,
+                           precision=precision)
         self.rc = self.ctx.run_config()
         self.batch = int(batch)
         self.seed = int(seed)
         self.dist = dist
         self.rank = dist.get_rank() if dist else 0
         self.world = dist.get_world_size() if dist else 1
-        self.log = log or Logger(enabled=self.rank == 0)
         if dist is not None and comm_backend == "nccl":  # RCCL communicator for the counter all-reduces
             from . import comm_unique_id
             uid = [comm_unique_id() if self.rank == 0 else None]
@@ -142,6 +144,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=int(os.environ.get("KML_SEED", "0")))
     ap.add_argument("--dist-backend", default=os.environ.get("KML_DIST_BACKEND", "nccl"),
                     help="nccl (RCCL over xGMI, one GPU per rank) or gloo (CPU counters; ranks may share a GPU)")
+    ap.add_argument("--precision", choices=["f64", "f32"], default=os.environ.get("KML_PRECISION", "f64"),
+                    help="BP decode arithmetic: f64 (default, bit-exact with the reference) or f32 (opt-in, "
+                         "PEG2304-class codes only, not bit-exact)")
     ap.add_argument("--force-dist", action="store_true", default=os.environ.get("KML_FORCE_DIST", "") == "1",
                     help="build the process group (and run its all-reduces) even when WORLD_SIZE is 1, "
                          "e.g. a 1-rank RCCL group under torchrun --nproc-per-node 1")
@@ -151,6 +156,8 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     log = Logger(enabled=rank == 0)
+    if args.precision != "f64":  # the first line of an f32 run states the mode; every other line keeps its format
+        log.info(f"BP decode precision: {args.precision} (single precision, not bit-exact with the reference)")
     log.info("Start simulation")
     if not os.path.exists(args.config):
         log.error("Encouter error while opening config.toml")
@@ -168,7 +175,7 @@ def main(argv=None):
             local = local % max(torch.cuda.device_count(), 1)
         dist = dist_mod
     sim = Simulator(args.config, device=local, batch=args.batch, seed=args.seed, dist=dist, log=log,
-                    comm_backend=args.dist_backend)
+                    comm_backend=args.dist_backend, precision=args.precision)
     sim.Simulate()
     sim.ctx.close()
     if dist is not None:
