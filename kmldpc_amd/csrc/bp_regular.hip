@@ -83,6 +83,42 @@ constexpr int kRedBytes = 16;
 #ifndef KML_REG_QUEUE_EARLY
 #define KML_REG_QUEUE_EARLY 1
 #endif
+// The VN phase of iteration 0 in closed form (FAST decodes only).  InitMsg sets
+// every c2v to (0.5, 0.5), and with a prior p in the FAST domain (+0, 1, or p
+// and 1 - p >= 2^(40 dv - 960): bp_common.hpp fast_prior_ok) the column chain
+// (binaryldpccodec.cc:177-212) is the identity on a = (p, RN(1 - p)):
+//   forward: n = (a0 / 2, a1 / 2), exact halvings (no subnormals in the
+//     domain); s = RN(a0 / 2 + a1 / 2) = RN(p + RN(1 - p)) / 2 = 1/2, because
+//     p + RN(1 - p) rounds to exactly 1 (bp_common.hpp, "first backward
+//     step"); (a0 / 2) / (1/2) = a0 exactly.  So every alpha, the column head
+//     included, is a, and the decision is a0 > a1 ? 0 : 1.
+//   backward: beta = (1, 1) gives t = a, sum 1, v2c = a; the next beta is
+//     (0.5, 0.5) / 1, then (0.25, 0.25) / 0.5 = (0.5, 0.5), ...: t = a / 2,
+//     sum 1/2, v2c = a.
+// Every v2c of the column is (p, RN(1 - p)) for any column degree
+// (tests/test_iter0_model.py restates the recursion in IEEE doubles): DV slot
+// stores and one decision byte per column, no division and nothing to prove,
+// so iteration 0 cannot raise the suspect flag itself (a forced one, sus0,
+// still reaches the first closing barrier).  The exact kernel keeps the
+// generic chain: its priors may be -0.0, subnormal or NaN, where the identity
+// fails.  Measured alone, same box: 9.02 -> 8.69 ms per step (-3.7%;
+// profiles/r07_ab_headline_summary.txt).
+#ifndef KML_REG_ITER0_CLOSED
+#define KML_REG_ITER0_CLOSED 1
+#endif
+// Without syndrome output (SYN = false) nothing the CN phase of the last
+// iteration of the budget writes is read again: the c2v slots feed only a next
+// VN phase, the chain states only the soft syndromes, and the reference returns
+// right after it (binaryldpccodec.cc:235-277).  What the decode still needs
+// from that phase is the parity check that rides on it (ret, conv, the
+// counters), so the phase loads the decision words of its half-rows (the high
+// dwords of the q1 values) and votes: no trellis, no c2v stores, no DPP state
+// swaps.  The phase still counts as run (iter, CNT_CN_PHASES).  Measured alone,
+// same box: 9.02 -> 8.93 ms per step (-1.0%); with the closed-form iteration
+// 0: 8.58 ms (-4.9%).
+#ifndef KML_REG_LAST_CN_PARITY
+#define KML_REG_LAST_CN_PARITY 1
+#endif
 constexpr int kRegMaxKw = 64;  // K <= N <= 2304 (bp_regular_threads): 36 words
 #if KML_STAMPS
 __device__ unsigned long long kml_reg_stamps[8];
@@ -169,7 +205,23 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     // The RV columns' chains are interleaved step by step in program order so
     // their dependent fma / rcp sequences overlap.  On the FAST path the
     // boundary state beta = (1, 1) is applied as the identity (x * 1.0 == x).
-    {
+    if (KML_REG_ITER0_CLOSED && FAST && iter == 0) {  // every v2c is the prior pair (proof at the switch)
+#pragma unroll
+      for (int r = 0; r < RV; ++r) {
+        // an opaque copy: 1 - p would otherwise be shared with the generic
+        // chain's and hoisted out of the iteration loop (RV more doubles live
+        // through it: +32 bytes of private segment)
+        double p = pv[r];
+        asm volatile("" : "+v"(p));
+        const double a1 = 1.0 - p;
+        const int hb = p > a1 ? 0 : 1;
+        const dbl2 m = dbl2{p, with_sign(a1, hb)};
+#pragma unroll
+        for (int k = 0; k < DV; ++k) lds_st<dbl2>(vaddr[r][k] & ~15u, m);
+        lds_st<unsigned char>(hd + r * T, (unsigned char)hb);
+      }
+      __builtin_amdgcn_s_setprio(0);
+    } else {
       // InitMsg (binaryldpccodec.cc:166-170): every c2v is 0.5 before the
       // first CN phase, so iteration 0 takes the constant instead of slots
       // initialised in LDS (every slot is written before it is read)
@@ -316,7 +368,16 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     // issued before the c2v STOREs (the partner's store of this step hits the
     // slot the lane is about to read), and LDS executes a wave's operations in
     // program order.
-    {
+    if (KML_REG_LAST_CN_PARITY && !SYN && iter + 1 == a.iter_count) {
+      // the budget's last CN phase without syndrome output: only the parity
+      // check is read (argument at the switch)
+#pragma unroll
+      for (int r = 0; r < RC; ++r) {
+        par[r] = 0;
+#pragma unroll
+        for (int st = 0; st < H; ++st) par[r] ^= lds_ld<unsigned>(rb[r] + st * 32 + 12);
+      }
+    } else {
       double x0[RC][H], x1[RC][H];  // lower-half chain states, kept for the swap
       double s0[RC], s1[RC];        // current chain state
 #pragma unroll
