@@ -58,8 +58,8 @@ $(STAMPS_LIB): $(STAMPS_OBJS)
 stamps: $(STAMPS_LIB)
 .PHONY: stamps
 
-# Experiment builds of the whole library with extra defines (A/B on one box):
-#   make variant V=<name> VFLAGS="-DKML_IRR_VN_PAIR_MAX=5"  -> kmldpc_amd/libkmldpc_amd_<name>.so
+# Instrumented builds of the whole library with extra defines:
+#   make variant V=divstats VFLAGS="-DKML_DIV_STATS=1"  -> kmldpc_amd/libkmldpc_amd_divstats.so
 VAR_DIR  := $(OBJDIR)/var_$(V)
 VAR_OBJS := $(addprefix $(VAR_DIR)/,$(addsuffix .o,$(CPP_SRCS) $(HIP_SRCS)))
 $(VAR_DIR)/%.o: $(CSRC)/%.cpp $(HDRS)

@@ -97,48 +97,25 @@ __device__ __forceinline__ double rcp_refine(double s) {
 // refinement is NOT RN(1/s) on six of these s (s = 1 - k 2^-53, k = 3, 5, ...,
 // 13: one ulp low), and hipcc's '/' then misrounds three significands (the
 // GPU test test_cn_reciprocal_exhaustive shows both).
-constexpr double kNearOne = 0x1p-40;
-#ifndef KML_CN_RANGE_CHECK
-#define KML_CN_RANGE_CHECK 0
-#endif
 // Two instructions: X * Y = 1 + 2^-78 exactly (X = 1 + 2^-26, Y = 1 - 2^-26 +
 // 2^-52), so fma(X, Y, 1 - s) is RN(1 + u + 2^-78) with one rounding — the
 // same tie-breaking as 1 + (u + 2^-80) without the third add.
 __device__ __forceinline__ double rcp_near1(double s) { return fma(0x1.0000004p+0, 0x1.ffffff8000002p-1, 1.0 - s); }
-// (see rcp_cn_rows for why the range check is off by default)
-__device__ __forceinline__ double rcp_cn(double s) {
-  double r = rcp_near1(s);
-#if KML_CN_RANGE_CHECK
-  if (__builtin_expect(!(fabs(1.0 - s) <= kNearOne), 0)) r = rcp_refine(s);
-#endif
-  return r;
-}
 
 // Reciprocals of the R sums of one CN step (R independent rows): the near-one
-// formula, or — when any sum of the lane is out of its range (not seen in a
-// CN phase) — hipcc's refinement for all R, as the other FAST divisions use.
-// One branch per step keeps the R rows' chains in one scheduling region.
+// formula, without a check that the sums are in its range (|s - 1| <= 2^-40).
 //
-// The range check is provably redundant on the FAST path: a CN sum is
+// Such a check is provably redundant on the FAST path: a CN sum is
 // RN(n0 + n1) with n0 = RN(RN(s0 m0) + RN(s1 m1)), n1 likewise, where (s0, s1)
 // and (m0, m1) are quotient pairs of one normalisation (each pair sums to
 // 1 within 2 ulps: RN(x0/S) + RN(x1/S) with S = RN(x0 + x1)) or the boundary
 // state (1, 0); the few roundings keep |s - 1| <= 16 * 2^-53 = 2^-49, far
 // inside 2^-40 (products that underflow are tiny beside the sum's dominant
-// terms).  KML_CN_RANGE_CHECK=1 builds keep it anyway (A/B, debugging).
+// terms).
 template <int R>
 __device__ __forceinline__ void rcp_cn_rows(const double (&s)[R], double (&r)[R]) {
 #pragma unroll
   for (int i = 0; i < R; ++i) r[i] = rcp_near1(s[i]);
-#if KML_CN_RANGE_CHECK
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < R; ++i) ok = ok & (fabs(1.0 - s[i]) <= kNearOne);
-  if (__builtin_expect(!ok, 0)) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) r[i] = rcp_refine(s[i]);
-  }
-#endif
 }
 // n / s from a reciprocal r of s that is exact for it (FAST division tail).
 __device__ __forceinline__ double qdiv_r(double n, double s, double r) {
@@ -233,7 +210,7 @@ __device__ __forceinline__ void div2(double n0, double n1, double s, double &q0,
     q0 = div_rn(n0, s);
     q1 = div_rn(n1, s);
   } else if constexpr (CN) {
-    const double r = rcp_cn(s);
+    const double r = rcp_near1(s);
     q0 = qdiv_r(n0, s, r);
     q1 = qdiv_r(n1, s, r);
   } else {
@@ -268,7 +245,7 @@ template <bool FAST, bool CN = true>
 __device__ __forceinline__ double div1(double n0, double s) {
   static_assert(CN, "div1 is the CN phase's division");
   if constexpr (!FAST) return div_rn(n0, s);
-  else return qdiv_r(n0, s, rcp_cn(s));
+  else return qdiv_r(n0, s, rcp_near1(s));
 }
 
 // The first backward step of a column multiplies beta = (1, 1) by the c2v pair

@@ -72,11 +72,8 @@ constexpr int kPartG = 4;
 // apart) then hit distinct banks (rows q and q + 4 no longer collide), and the
 // VN phase's scattered ds_read_b64 use all 64 banks instead of the 32 of
 // slot-aligned addresses.  vaddr holds the half-slot index 2 slot + half.
-#ifndef KML_PART_C2V_HALF
-#define KML_PART_C2V_HALF 1
-#endif
 __host__ __device__ constexpr int part_c2v_half(int slot, int EG, int DC) {
-  return KML_PART_C2V_HALF ? (slot < EG ? ((slot / DC) >> 2) & 1 : (slot >> 2) & 1) : 0;
+  return slot < EG ? ((slot / DC) >> 2) & 1 : (slot >> 2) & 1;
 }
 __device__ __forceinline__ unsigned vaddr_c2v(int v) { return (unsigned)(v & 0x1FFFF) * 8u; }  // c2v word (bytes)
 __device__ __forceinline__ unsigned vaddr_slot(int v) { return (unsigned)(v & 0x1FFFE) * 8u; }  // slot (bytes)
@@ -91,9 +88,8 @@ size_t part_lds_bytes(const DevCode &c) {
   return ((size_t)c.M / c.pt_G * 6 + (size_t)c.pt_mirror + kPartDummy) * 16 + (size_t)c.N;
 }
 
-#ifndef KML_POLL_SLEEP  // (A/B) s_sleep between the tagged mailbox polls
-#define KML_POLL_SLEEP 0  // measured: no sleep 8.52 -> 8.48 ms per 4096 PEG8064 codewords
-#endif
+// (the tagged mailbox polls spin without an s_sleep between them: measured
+// 8.52 -> 8.48 ms per 4096 PEG8064 codewords)
 constexpr long long kSpinLimit = 20000000;  // ~1 s of s_sleep(1) polls
 
 // The tagged mailboxes (bp_part_kernel) follow the barrier-exchange ones in
@@ -153,7 +149,10 @@ __device__ __forceinline__ double swap_pair(double x) {
 }
 __device__ __forceinline__ int swap_pair_i(int x) { return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false); }
 
-#ifdef KML_STAMPS
+#ifndef KML_STAMPS
+#define KML_STAMPS 0
+#endif
+#if KML_STAMPS
 // Phase timing of the partitioned kernel (a KML_STAMPS=1 build only): wave 0
 // of every workgroup adds s_memtime deltas per phase of its iterations.
 constexpr int kStampSlots = 10;
@@ -273,7 +272,7 @@ __device__ __forceinline__ int part_iterations(const BpLaunch &a, int M, int N, 
   double2 *slots = reinterpret_cast<double2 *>(smem);
   int iter = 0;
   bool conv = false, sus = sus0;
-#ifdef KML_STAMPS
+#if KML_STAMPS
   unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
 #endif
   for (; iter < a.iter_count; ++iter) {
@@ -284,7 +283,7 @@ __device__ __forceinline__ int part_iterations(const BpLaunch &a, int M, int N, 
       for (int q = 0; q < RX; ++q)
         if (xc[q] >= 0) {
           const int sl = xc[q] & 0xFFFF;
-          *reinterpret_cast<double *>(smem + sl * 16 + (KML_PART_C2V_HALF ? ((sl >> 2) & 1) * 8 : 0)) =
+          *reinterpret_cast<double *>(smem + sl * 16 + ((sl >> 2) & 1) * 8) =
               ld_nt(&mb_c2v[xc[q] >> 16]);
         }
       __syncthreads();
@@ -511,18 +510,7 @@ __device__ __forceinline__ int part_iterations(const BpLaunch &a, int M, int N, 
 // the v2c of iteration g + 2, which its partners send after their iteration
 // g + 1 flag polls.  Measured against the CN-closing-barrier form (flags
 // checked before the next VN): see DESIGN.md.
-#ifndef KML_PART_CN_AGE_PRIO
-#define KML_PART_CN_AGE_PRIO 5
-#endif
-#ifndef KML_PART_FLAG_LATE  // (A/B) 0: the last wave of the CN phase posts the flag (returned LDS atomics)
-#define KML_PART_FLAG_LATE 1
-#endif
-#ifndef KML_PART_VN_AGE_PRIO
-#define KML_PART_VN_AGE_PRIO 0
-#endif
-#ifndef KML_PART_QUEUE_EARLY  // the next entry taken under the outputs (bp_part_kernel's loop)
-#define KML_PART_QUEUE_EARLY 1
-#endif
+constexpr int kPartCnAgePrio = 5;  // the tagged CN phase's priorities by wave age until this step
 constexpr unsigned kTagHi = 0x80000000u;  // bit 63 of a message word (hi dword bit 31)
 constexpr unsigned kHdHi = 0x40000000u;   // bit 62: hard decision (v2c first word)
 
@@ -605,7 +593,7 @@ __device__ __forceinline__ bool poll_entries(const int (&ent)[R], __amdgpu_buffe
           // stored without the tags (a v2c message keeps its hard-decision bit)
           const int sl = ent[q] & 0xFFFF;
           unsigned long long *d = reinterpret_cast<unsigned long long *>(
-              smem + sl * 16 + (W == 1 && KML_PART_C2V_HALF ? ((sl >> 2) & 1) * 8 : 0));
+              smem + sl * 16 + (W == 1 ? ((sl >> 2) & 1) * 8 : 0));
 #pragma unroll
           for (int i = 0; i < W; ++i) d[i] = w[q][i] & ~(1ull << 63);
           need[q] = false;
@@ -618,7 +606,6 @@ __device__ __forceinline__ bool poll_entries(const int (&ent)[R], __amdgpu_buffe
       coop_abort(abort, W == 2 ? kAbortV2c : kAbortC2v, spin > kSpinLimit);
       return false;
     }
-    if (KML_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
   }
 }
 
@@ -637,10 +624,6 @@ __device__ __forceinline__ int part_iterations_tagged(
     int odd, int &iter_out, bool &conv_out, int &pcnt_out, int &decbuf_out, bool sus0 = false) {
   constexpr int DV = 3, DC = 6, H = 3, NW = T / 64;
   const int tid = threadIdx.x;
-#if !KML_PART_FLAG_LATE
-  __shared__ int sarrive;  // waves done with the CN phase of this iteration
-  if (tid == 0) sarrive = 0;
-#endif
   __shared__ int sany;     // bit 0: some member had failing rows after the previous CN phase; bit 1: an unproven quotient
   int iter = 0, pcnt_prev = 0;
   bool sus = sus0;
@@ -648,7 +631,7 @@ __device__ __forceinline__ int part_iterations_tagged(
 #pragma unroll
   for (int r = 0; r < RC; ++r) syn_prev[r] = 0.0;
   bool conv = false;
-#ifdef KML_STAMPS
+#if KML_STAMPS
   unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
 #endif
   for (;; ++iter, ++g) {
@@ -666,17 +649,7 @@ __device__ __forceinline__ int part_iterations_tagged(
     // (c2v of cut edges sit in the mirror slots, received at the end of the
     // previous iteration; iteration 0 reads InitMsg's 0.5)
     if (run) {
-#if KML_PART_VN_AGE_PRIO  // (A/B) VN priorities by wave age for the whole phase (measured +5%: off)
-      {
-        const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 4 / NW;
-        if (grp >= 3) __builtin_amdgcn_s_setprio(3);
-        else if (grp == 2) __builtin_amdgcn_s_setprio(2);
-        else if (grp == 1) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      }
-#else
-      __builtin_amdgcn_s_setprio(3);
-#endif
+      __builtin_amdgcn_s_setprio(3);  // (VN priorities by wave age for the whole phase measured +5%)
       // one column's chains at a time (column-major): the FAST divisions'
       // proofs keep a normalisation's operands live, and interleaving the RV
       // columns step by step doubled the live set (scratch spills in the loop)
@@ -807,9 +780,8 @@ __device__ __forceinline__ int part_iterations_tagged(
         par[r] = 0;
       }
 // (the tagged CN phase's wave priorities by age, youngest quarter highest,
-// until step KML_PART_CN_AGE_PRIO, then 0: 8.69 -> 8.54 ms per 4096 PEG8064
-// codewords against falling-by-step priorities (0), as in bp_regular.hip)
-#if KML_PART_CN_AGE_PRIO
+// until step kPartCnAgePrio, then 0: 8.69 -> 8.54 ms per 4096 PEG8064
+// codewords against falling-by-step priorities, as in bp_regular.hip)
       {
         const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 4 / NW;  // 0 oldest .. 3 youngest
         if (grp >= 3) __builtin_amdgcn_s_setprio(3);
@@ -817,17 +789,9 @@ __device__ __forceinline__ int part_iterations_tagged(
         else if (grp == 1) __builtin_amdgcn_s_setprio(1);
         else __builtin_amdgcn_s_setprio(0);
       }
-#else
-      __builtin_amdgcn_s_setprio(2);
-#endif
 #pragma unroll
       for (int st = 0; st < DC; ++st) {
-#if KML_PART_CN_AGE_PRIO
-        if (st == KML_PART_CN_AGE_PRIO) __builtin_amdgcn_s_setprio(0);
-#else
-        if (st == 2) __builtin_amdgcn_s_setprio(1);
-        if (st == 4) __builtin_amdgcn_s_setprio(0);
-#endif
+        if (st == kPartCnAgePrio) __builtin_amdgcn_s_setprio(0);
         const bool advance = SYN || st + 1 < DC || st < H;
         double m0[RC], m1[RC];
         if (advance) {
@@ -891,35 +855,21 @@ __device__ __forceinline__ int part_iterations_tagged(
     pcnt_prev = nfail;  // unsatisfied checks of this iteration's hard decisions (final if the loop ends after it)
     const int wbits = (__ballot(fail) != 0 ? 1 : 0) | (__ballot(sus) != 0 ? 2 : 0);
     KML_STAMP(6);
-#if KML_PART_FLAG_LATE
     // every wave ORs its bits in (no returned atomic on its path); thread 0
     // posts the member's flag after the closing barrier below — the partners
     // read it only after their next VN phase and v2c receive
     if ((tid & 63) == 0 && wbits) atomicOr(sfail, wbits);
-#else
-    if ((tid & 63) == 0) {  // the member's last wave to get here posts its flag
-      if (wbits) atomicOr(sfail, wbits);
-      if (atomicAdd(&sarrive, 1) == NW - 1) {
-        const int f = atomicExch(sfail, 0);
-        sarrive = 0;
-        __hip_atomic_store(&gs->mflag[g & 1][member], ((unsigned long long)(g + 1) << 2) | (unsigned long long)(f & 3),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-#endif
     KML_STAMP(7);
     // --------------------------------------- receive c2v of the cut edges
     if (iter + 1 < a.iter_count)
       if (!poll_entries<RX, 1>(xc, tb, tb_c2v, smem, tag, abort)) *sdead = 1;
     __syncthreads();
-#if KML_PART_FLAG_LATE
     if (tid == 0) {
       const int f = *sfail;
       *sfail = 0;
       __hip_atomic_store(&gs->mflag[g & 1][member], ((unsigned long long)(g + 1) << 2) | (unsigned long long)(f & 3),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#endif
     KML_STAMP(8);
     if (*sdead) return -1;
   }
@@ -1032,7 +982,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1))) void bp_
   // from the device (a.B_dev).
   const int B = a.B_dev ? (int)*a.B_dev : a.B;  // (read again: every read sees the finished count)
 
-  // KML_PART_QUEUE_EARLY: after a decoded codeword, member 0 has taken the
+  // After a decoded codeword, member 0 has taken the
   // next entry during the outputs and published it before their closing
   // barrier, and clears the sums after reading them, so the next codeword
   // starts without a group barrier; after a deferred codeword (no outputs, a
@@ -1050,7 +1000,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1))) void bp_
     } else if (tid == 0) {
       spcnt = 0;  // (read by this thread before the outputs' closing barrier)
     }
-    top_sync = !KML_PART_QUEUE_EARLY;
+    top_sync = false;
     const int entry = (int)ld_rlx(&gs->cw);
     if (entry >= B) break;
     // a deferred entry with bit 31 set: a codeword the tagged launch stopped on
@@ -1127,8 +1077,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1))) void bp_
     }
 
     // ---- outputs
-    unsigned nxt = 0;  // KML_PART_QUEUE_EARLY: the next entry, in flight through the outputs
-    if (KML_PART_QUEUE_EARLY && member == 0 && tid == 0) nxt = atomicAdd(queue, 1u);
+    unsigned nxt = 0;  // the next entry, in flight through the outputs
+    if (member == 0 && tid == 0) nxt = atomicAdd(queue, 1u);
     if (a.iter_count > 0) {
       if constexpr (tagged) {
         // a member holds the decisions of its own columns (double-buffered by
@@ -1193,16 +1143,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1))) void bp_
       }
     }
     // (every member read gs->cw at this codeword's start, several barriers ago)
-    if (KML_PART_QUEUE_EARLY && member == 0 && tid == 0)
+    if (member == 0 && tid == 0)
       __hip_atomic_store(&gs->cw, nxt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (part_barrier<kG>(gs, bst, nb, same_xcd, abort, nullptr) < 0) return;  // the members' sums are complete
     if (member == 0 && tid == 0) {
       const int errs = (int)ld_rlx(&gs->errs);
       const int pc = (int)ld_rlx(&gs->pcnt);
-      if (KML_PART_QUEUE_EARLY) {  // no member adds to the sums before the next codeword's flag barrier
-        __hip_atomic_store(&gs->errs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&gs->pcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      // no member adds to the sums before the next codeword's flag barrier
+      __hip_atomic_store(&gs->errs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&gs->pcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (a.ret) a.ret[cw] = iter + (iter < a.max_iter);
       if (a.iters) a.iters[cw] = iter;
       if (a.parity_cnt) a.parity_cnt[cw] = a.iter_count > 0 ? pc : 0;
@@ -1297,16 +1246,6 @@ hipError_t launch_part_chain(const DevCode &c, const BpLaunch &a, const BpLaunch
   return launch_part_t<kG, T_, R_, R_, X_, SYN, false, true>(c, be, s, 0, groups, false);
 }
 
-// Tiling of the partitioned kernel: KML_PART = threads per workgroup (512,
-// 768 or 1024; default 1024).
-int part_threads() {
-  if (const char *e = getenv("KML_PART")) {
-    const int t = atoi(e);
-    if (t == 512 || t == 768 || t == 1024) return t;
-  }
-  return 1024;
-}
-
 }  // namespace
 
 size_t bp_coop_sync_bytes(int groups) { return part_defer_offset(groups) + 16; }
@@ -1337,7 +1276,7 @@ int bp_coop_groups(const DevCode &c) {
   return (ncu / (8 * kPartG)) * 8;  // 8 XCDs, groups of 4 per XCD
 }
 
-#ifdef KML_STAMPS
+#if KML_STAMPS
 }  // namespace kml
 extern "C" int kml_debug_part_stamps(unsigned long long *out, int reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(kml::kml_part_stamps), sizeof(kml::kml_part_stamps));
@@ -1358,7 +1297,6 @@ hipError_t launch_bp_coop(const DevCode &c, const BpLaunch &a, hipStream_t s) {
   if (const char *k = getenv("KML_BP_KERNEL"))
     if (k[0] == 'g') return hipErrorNotSupported;
   const int fast = bp_fast_mode(c);
-  const int T = part_threads();
   {
     // exchange entries per thread: every member's lists must fit RX * T
     int xmax = 0;
@@ -1379,15 +1317,11 @@ hipError_t launch_bp_coop(const DevCode &c, const BpLaunch &a, hipStream_t s) {
       hipError_t e = hipMemsetAsync(d.defer_cnt, 0, sizeof(unsigned), s);
       if (e != hipSuccess) return e;
     }
-#define KML_PART_CASE(G_, T_, R_, X_)                \
-  if (T == T_ && xmax <= X_ * T_) \
-    return a.syn ? launch_part_chain<G_, T_, R_, X_, true>(c, a, d, s, fast, groups, tagged) \
-                 : launch_part_chain<G_, T_, R_, X_, false>(c, a, d, s, fast, groups, tagged);
-    KML_PART_CASE(4, 512, 4, 4)
-    KML_PART_CASE(4, 768, 3, 3)
-    KML_PART_CASE(4, 1024, 2, 2)
-#undef KML_PART_CASE
-    return hipErrorNotSupported;
+    // the one tiling: 1024 threads per member, two columns, half-rows and
+    // exchange entries per thread (512 and 768 threads measured slower: DESIGN.md)
+    if (xmax > 2 * 1024) return hipErrorNotSupported;
+    return a.syn ? launch_part_chain<4, 1024, 2, 2, true>(c, a, d, s, fast, groups, tagged)
+                 : launch_part_chain<4, 1024, 2, 2, false>(c, a, d, s, fast, groups, tagged);
   }
 }
 

@@ -54,7 +54,7 @@ __device__ __forceinline__ double with_sign(double x, int bit) {
 }
 __device__ __forceinline__ int swap_pair_i(int x) { return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false); }
 
-// Beta chains ahead (R <= KML_IRR_VN_BETA_EARLY_R): a column's backward
+// Beta chains ahead (single columns, R == 1): a column's backward
 // states beta_k (binaryldpccodec.cc:199-213: beta_{D-1} = (1, 1), beta_{k-1} =
 // normalise(beta_k * c2v_k)) depend on the c2v messages only, not on the
 // forward alphas, so the two chains run interleaved step by step and the
@@ -64,9 +64,6 @@ __device__ __forceinline__ int swap_pair_i(int x) { return __builtin_amdgcn_mov_
 // in another order; the betas are held (2 D more registers).  A wave holding
 // the heaviest columns alone at the end of the VN phase runs latency-bound
 // (profiles/r05_v4_irr_stamps.txt: waves 0-2, degree 9).
-#ifndef KML_IRR_VN_BETA_EARLY_R
-#define KML_IRR_VN_BETA_EARLY_R 1
-#endif
 template <int D, int R, bool FAST>
 __device__ __forceinline__ void vn_cols_beta_early(double2 *slots, const unsigned short *const (&cs)[R],
                                                    const double (&p)[R], unsigned char *const (&hard)[R], bool &sus) {
@@ -133,7 +130,7 @@ __device__ __forceinline__ void vn_cols_beta_early(double2 *slots, const unsigne
 template <int D, int R, bool FAST>
 __device__ __forceinline__ void vn_cols(double2 *slots, const unsigned short *const (&cs)[R], const double (&p)[R],
                                         unsigned char *const (&hard)[R], bool &sus) {
-  if constexpr (R <= KML_IRR_VN_BETA_EARLY_R && D > 2) {
+  if constexpr (R == 1 && D > 2) {
     vn_cols_beta_early<D, R, FAST>(slots, cs, p, hard, sus);
     return;
   }
@@ -268,32 +265,6 @@ __device__ __forceinline__ void cn_halves(double2 *slots, const int (&base)[R], 
   for (int r = 0; r < R; ++r) sv[r] = s0[r];
 }
 
-// falling wave priorities over a phase's rounds (see bp_regular.hip);
-// the levels are overridable for A/B builds
-#ifndef KML_IRR_PRIO_VN_PAIR
-#define KML_IRR_PRIO_VN_PAIR 3
-#endif
-#ifndef KML_IRR_PRIO_VN_SINGLE
-#define KML_IRR_PRIO_VN_SINGLE 1
-#endif
-#ifndef KML_IRR_PRIO_CN_PAIR
-#define KML_IRR_PRIO_CN_PAIR 2
-#endif
-#ifndef KML_IRR_CN_AGE_PRIO
-#define KML_IRR_CN_AGE_PRIO 0
-#endif
-#ifndef KML_IRR_PRIO_CN_SINGLE
-#define KML_IRR_PRIO_CN_SINGLE 0
-#endif
-__device__ __forceinline__ void set_prio(int p) {
-  switch (p) {
-    case 3: __builtin_amdgcn_s_setprio(3); break;
-    case 2: __builtin_amdgcn_s_setprio(2); break;
-    case 1: __builtin_amdgcn_s_setprio(1); break;
-    default: __builtin_amdgcn_s_setprio(0); break;
-  }
-}
-
 // Degree dispatch.  Paired (R = 2) instances exist up to the plan's pair
 // limits (kIrrVnPairMax / kIrrCnPairMax): the register budget of three waves
 // per SIMD holds two interleaved chains only up to those degrees.
@@ -415,7 +386,8 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
       asm volatile("" : "+v"(vp[r]), "+v"(cp[r]));
     }
     asm volatile("" : "+v"(od));
-    set_prio(KML_IRR_PRIO_VN_PAIR);
+    // falling wave priorities over a phase's rounds (see bp_regular.hip): VN 3 then 1, CN 2 then 0
+    __builtin_amdgcn_s_setprio(3);
     if (vp[0] != ~0u) {  // paired round: two columns of one degree, interleaved
       const int v0 = pitem(vp[0]), v1 = pitem(vp[1]);
       const unsigned short *const cs[2] = {cslot + pbase(vp[0]), cslot + pbase(vp[1])};
@@ -424,7 +396,7 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
       vn_any<2, FAST>(pdeg(vp[0]), slots, cs, p, h, sus);
     }
     IRR_STAMP(0);
-    set_prio(KML_IRR_PRIO_VN_SINGLE);
+    __builtin_amdgcn_s_setprio(1);
     if (vp[2] != ~0u) {
       const int v = pitem(vp[2]);
       const unsigned short *const cs[1] = {cslot + pbase(vp[2])};
@@ -444,11 +416,7 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
     double sv[3] = {0.0, 0.0, 0.0};
     unsigned par[3] = {0u, 0u, 0u};
     IRR_STAMP(3);
-#if KML_IRR_CN_AGE_PRIO  // (A/B) the CN pair round's priority by wave age (youngest third highest)
-    set_prio(1 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 3 / (T / 64));
-#else
-    set_prio(KML_IRR_PRIO_CN_PAIR);
-#endif
+    __builtin_amdgcn_s_setprio(2);
     if (cp[0] != ~0u) {  // both lanes of a pair agree
       const int base[2] = {pbase(cp[0]), pbase(cp[1])};
       double s2[2];
@@ -460,7 +428,7 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
       par[1] = p2[1];
     }
     IRR_STAMP(4);
-    set_prio(KML_IRR_PRIO_CN_SINGLE);
+    __builtin_amdgcn_s_setprio(0);
     if (cp[2] != ~0u) {
       const int base[1] = {pbase(cp[2])};
       double s1[1];

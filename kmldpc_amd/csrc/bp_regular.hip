@@ -25,7 +25,7 @@
 //     the halves through the same DPP swap; the workgroup OR is one barrier
 //     (bp_common.hpp wg_any).
 //   * wave priorities: falling by step in the VN phase, by wave age in the CN
-//     phase (KML_CN_AGE_PRIO).
+//     phase (kCnAgePrio).
 //   * LDS placement (layout.hpp): the columns' lane assignment is annealed on
 //     the host against the VN phase's bank conflicts, the hard decisions are
 //     stored by lane position (contiguous byte stores), rows are stored in CN
@@ -61,28 +61,20 @@ constexpr int kRedBytes = 16;
 // highest) until step s, then all at 0 — the oldest waves otherwise win the
 // arbiter's age tie-break and finish 1.2K cycles before the youngest (per-wave
 // stamps); measured 5 (-0.7..0.9%) against falling-by-step (0), 2, 3 and 6.
-#ifndef KML_CN_AGE_PRIO
-#define KML_CN_AGE_PRIO 5
-#endif
-#ifndef KML_VN_AGE_PRIO  // (A/B) 1: VN priorities by wave age for the whole phase (measured +4%: off)
-#define KML_VN_AGE_PRIO 0
-#endif
+// VN priorities by wave age for the whole phase measured +4%: they fall by step.
+constexpr int kCnAgePrio = 5;
 // Epilogue latency (stamps: 5.4 K + 1.3 K of ~180 K cycles per codeword): the
 // codeword's reference bits for CntErr go straight from global memory into LDS
 // in its prologue (global_load_lds: no register holds them, the latency hides
 // under the demap / prior check instead of opening the epilogue), and the
 // workgroup sums its counters in LDS, flushed with one global atomic each when
 // the workgroup leaves.
-#ifndef KML_REG_EPI_LDS
-#define KML_REG_EPI_LDS 1
-#endif
+//
 // The next queue entry is taken at the start of a codeword's epilogue (thread
 // 0's atomic in flight under CntErr and the epilogue's barrier) instead of
 // between two barriers at the top of the loop: one barrier and the atomic's
 // round trip leave the per-codeword critical path.
-#ifndef KML_REG_QUEUE_EARLY
-#define KML_REG_QUEUE_EARLY 1
-#endif
+//
 // The VN phase of iteration 0 in closed form (FAST decodes only).  InitMsg sets
 // every c2v to (0.5, 0.5), and with a prior p in the FAST domain (+0, 1, or p
 // and 1 - p >= 2^(40 dv - 960): bp_common.hpp fast_prior_ok) the column chain
@@ -103,9 +95,7 @@ constexpr int kRedBytes = 16;
 // generic chain: its priors may be -0.0, subnormal or NaN, where the identity
 // fails.  Measured alone, same box: 9.02 -> 8.69 ms per step (-3.7%;
 // profiles/r07_ab_headline_summary.txt).
-#ifndef KML_REG_ITER0_CLOSED
-#define KML_REG_ITER0_CLOSED 1
-#endif
+//
 // Without syndrome output (SYN = false) nothing the CN phase of the last
 // iteration of the budget writes is read again: the c2v slots feed only a next
 // VN phase, the chain states only the soft syndromes, and the reference returns
@@ -116,9 +106,6 @@ constexpr int kRedBytes = 16;
 // swaps.  The phase still counts as run (iter, CNT_CN_PHASES).  Measured alone,
 // same box: 9.02 -> 8.93 ms per step (-1.0%); with the closed-form iteration
 // 0: 8.58 ms (-4.9%).
-#ifndef KML_REG_LAST_CN_PARITY
-#define KML_REG_LAST_CN_PARITY 1
-#endif
 constexpr int kRegMaxKw = 64;  // K <= N <= 2304 (bp_regular_threads): 36 words
 #if KML_STAMPS
 __device__ unsigned long long kml_reg_stamps[8];
@@ -169,9 +156,6 @@ __device__ __forceinline__ double with_sign(double x, int bit) {
 // before that iteration's syndromes are written, so everything a suspect
 // decode wrote (slots, decisions, syndromes of earlier iterations) is what the
 // exact decode rewrites identically or overwrites.
-#ifndef KML_REG_VN_COLMAJOR
-#define KML_REG_VN_COLMAJOR 1
-#endif
 template <int T, int RV, int RC, int DV, int DC, bool SYN, bool FAST>
 __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, int cw, unsigned char *smem,
                                            unsigned hd, const unsigned (&vaddr)[RV][DV], const double (&pv)[RV],
@@ -192,20 +176,11 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     // the 3 waves of a SIMD reach the barrier together instead of the oldest
     // finishing first and the youngest running its dependent chains alone.
     // Measured: per-phase end-time spread 3100 -> 500 cycles, kernel -2.5%.
-#if KML_VN_AGE_PRIO
-    {
-      const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) / 4;  // 0 oldest .. 2 youngest
-      if (grp >= 2) __builtin_amdgcn_s_setprio(3);
-      else if (grp == 1) __builtin_amdgcn_s_setprio(2);
-      else __builtin_amdgcn_s_setprio(1);
-    }
-#else
     __builtin_amdgcn_s_setprio(3);
-#endif
     // The RV columns' chains are interleaved step by step in program order so
     // their dependent fma / rcp sequences overlap.  On the FAST path the
     // boundary state beta = (1, 1) is applied as the identity (x * 1.0 == x).
-    if (KML_REG_ITER0_CLOSED && FAST && iter == 0) {  // every v2c is the prior pair (proof at the switch)
+    if (FAST && iter == 0) {  // every v2c is the prior pair (proof above: "The VN phase of iteration 0")
 #pragma unroll
       for (int r = 0; r < RV; ++r) {
         // an opaque copy: 1 - p would otherwise be shared with the generic
@@ -230,7 +205,6 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
       for (int r = 0; r < RV; ++r)
 #pragma unroll
         for (int k = 0; k < DV; ++k) c0s[r][k] = iter == 0 ? 0.5 : lds_ld<double>(vaddr[r][k]);
-#if KML_REG_VN_COLMAJOR
       // one column's chains at a time (registers: see bp_coop.hip).  FAST: the
       // column's quotients unsettled (div2 DEFER), and in the rare case that
       // one of them could not be proven the column runs again settling each
@@ -285,68 +259,6 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
       }
       __builtin_amdgcn_s_setprio(0);
     }
-#else
-      double a0[RV], a1[RV], al0[RV][DV], al1[RV][DV];
-      int hb[RV];
-#pragma unroll
-      for (int r = 0; r < RV; ++r) {
-        a0[r] = pv[r];
-        a1[r] = 1.0 - pv[r];
-      }
-#pragma unroll
-      for (int k = 0; k < DV; ++k)
-#pragma unroll
-        for (int r = 0; r < RV; ++r) {
-          al0[r][k] = a0[r];
-          al1[r][k] = a1[r];
-          const double c0 = c0s[r][k];
-          const double n0 = a0[r] * c0;
-          const double n1 = a1[r] * (1.0 - c0);
-          if (k + 1 < DV)
-            div2<FAST>(n0, n1, n0 + n1, a0[r], a1[r], sus);
-          else {  // the posterior only feeds the hard decision
-            hb[r] = hard_decision<FAST>(n0, n1, sus);
-            lds_st<unsigned char>(hd + r * T, (unsigned char)hb[r]);
-          }
-        }
-      double b0[RV], b1[RV];
-#pragma unroll
-      for (int r = 0; r < RV; ++r) b0[r] = b1[r] = 1.0;
-#if !KML_VN_AGE_PRIO
-      __builtin_amdgcn_s_setprio(2);
-#endif
-#pragma unroll
-      for (int k = DV - 1; k >= 0; --k) {
-#if !KML_VN_AGE_PRIO
-        if (k == DV - 2) __builtin_amdgcn_s_setprio(1);
-        if (k == DV - 3) __builtin_amdgcn_s_setprio(0);
-#endif
-#pragma unroll
-        for (int r = 0; r < RV; ++r) {
-          const bool unit = FAST && k == DV - 1;  // beta = (1, 1)
-          const double t0 = unit ? al0[r][k] : al0[r][k] * b0[r];
-          const double t1 = unit ? al1[r][k] : al1[r][k] * b1[r];
-          double q0, q1;
-          if (unit)  // beta = (1, 1): t is the normalised alpha, its sum within ulps of 1 (bp_common.hpp rcp_near1)
-            div2<FAST, true>(t0, t1, t0 + t1, q0, q1, sus);
-          else
-            div2<FAST>(t0, t1, t0 + t1, q0, q1, sus);
-          // the column's decision rides in the sign bit of q1 (a probability,
-          // >= +0): the CN chains that load the message collect the parity
-          lds_st<dbl2>(vaddr[r][k] & ~15u, dbl2{q0, with_sign(q1, hb[r])});
-          if (k > 0) {
-            const double c0 = c0s[r][k];
-            if (unit) {  // (c0, 1 - c0) / (c0 + (1 - c0)): the sum rounds to exactly 1 (bp_common.hpp)
-              b0[r] = c0;
-              b1[r] = 1.0 - c0;
-            } else {
-              div2<FAST>(b0[r] * c0, b1[r] * (1.0 - c0), b0[r] * c0 + b1[r] * (1.0 - c0), b0[r], b1[r], sus);
-            }
-          }
-        }
-      }
-    }
-#endif
     REG_WSTAMP(0);
     __syncthreads();
     REG_WSTAMP(1);
@@ -368,9 +280,9 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     // issued before the c2v STOREs (the partner's store of this step hits the
     // slot the lane is about to read), and LDS executes a wave's operations in
     // program order.
-    if (KML_REG_LAST_CN_PARITY && !SYN && iter + 1 == a.iter_count) {
+    if (!SYN && iter + 1 == a.iter_count) {
       // the budget's last CN phase without syndrome output: only the parity
-      // check is read (argument at the switch)
+      // check is read (argument above: "Without syndrome output")
 #pragma unroll
       for (int r = 0; r < RC; ++r) {
         par[r] = 0;
@@ -386,24 +298,15 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
         s1[r] = 0.0;
         par[r] = 0;
       }
-#if KML_CN_AGE_PRIO  // (A/B) the youngest waves start the CN phase at the highest priority
-      {
+      {  // the youngest waves start the CN phase at the highest priority
         const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) / 4;  // 0 oldest .. 2 youngest
         if (grp >= 2) __builtin_amdgcn_s_setprio(3);
         else if (grp == 1) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(1);
       }
-#else
-      __builtin_amdgcn_s_setprio(2);
-#endif
 #pragma unroll
       for (int st = 0; st < DC; ++st) {
-#if KML_CN_AGE_PRIO
-        if (st == KML_CN_AGE_PRIO) __builtin_amdgcn_s_setprio(0);
-#else
-        if (st == 2) __builtin_amdgcn_s_setprio(1);
-        if (st == 4) __builtin_amdgcn_s_setprio(0);
-#endif
+        if (st == kCnAgePrio) __builtin_amdgcn_s_setprio(0);
         const bool advance = SYN || st + 1 < DC;
         double m0[RC], m1[RC];
         if (advance) {
@@ -511,8 +414,8 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
   // fused demap: the constellation and the exp table in LDS (demap_common.hpp)
   __shared__ double dcons[DMB > 0 ? (2 << DMB) : 2];
   __shared__ uint64_t detab[DMB > 0 ? 256 : 1];
-  __shared__ uint64_t refw[kRegMaxKw];                  // KML_REG_EPI_LDS: this codeword's reference bits
-  __shared__ unsigned long long wcnt[CNT_CONVERGED + 1];  // KML_REG_EPI_LDS: the workgroup's counters
+  __shared__ uint64_t refw[kRegMaxKw];                    // this codeword's reference bits
+  __shared__ unsigned long long wcnt[CNT_CONVERGED + 1];  // the workgroup's counters
   double *p0s = reinterpret_cast<double *>(smem + p0s_offset(c.E, c.N));
   if constexpr (DMB > 0) {
     for (int k = threadIdx.x; k < (2 << DMB); k += T) dcons[k] = a.sym_cons[k];
@@ -559,24 +462,15 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
   unsigned long long rs_prev = __builtin_amdgcn_s_memtime(), rs_acc[8] = {};
 #endif
   const int B = a.B_dev ? (int)*a.B_dev : a.B;  // the exact kernel: the FAST kernel's defer count
-  const bool cnt_lds = KML_REG_EPI_LDS && a.counters;
-  const bool ref_pre = KML_REG_EPI_LDS && a.ref_bits && a.iter_count > 0;  // (c.Kw <= kRegMaxKw: host check)
-  if (cnt_lds && tid <= CNT_CONVERGED) wcnt[tid] = 0;  // ordered by the loop's first barrier
-  if (KML_REG_QUEUE_EARLY && tid == 0) {  // the first entry; then each codeword's epilogue takes the next
+  const bool ref_pre = a.ref_bits && a.iter_count > 0;  // (c.Kw <= kRegMaxKw: host check)
+  if (a.counters && tid <= CNT_CONVERGED) wcnt[tid] = 0;  // ordered by the loop's first barrier
+  if (tid == 0) {  // the first entry; then each codeword's epilogue takes the next
     red[3] = (int)atomicAdd(queue, 1u);
     red[0] = 0;
     red[1] = 0;
   }
   for (;;) {
     __syncthreads();
-    if (!KML_REG_QUEUE_EARLY) {
-      if (tid == 0) {
-        red[3] = (int)atomicAdd(queue, 1u);
-        red[0] = 0;
-        red[1] = 0;
-      }
-      __syncthreads();
-    }
     const int entry = red[3];
     REG_STAMP(0);
     if (entry >= B) break;
@@ -596,10 +490,10 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
         const double2 v = yy[j];
         double out[DMB];
         if constexpr (EXACT)
-          demap_symbol_t<DMB, false, lds_cons, 2, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x, hh.y,
+          demap_symbol_t<DMB, false, lds_cons, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x, hh.y,
                                                           a.sym_var, out);
         else  // no exact fallback in the FAST kernel (its registers): a failing symbol defers the codeword
-          dok &= demap_symbol_t<DMB, true, lds_cons, 2, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x,
+          dok &= demap_symbol_t<DMB, true, lds_cons, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x,
                                                               hh.y, a.sym_var, out);
 #pragma unroll
         for (int b = 0; b < DMB; ++b) p0s[j * DMB + b] = out[b];
@@ -636,7 +530,7 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
       if (defer) {
         if (tid == 0) {
           a.defer_idx[atomicAdd(a.defer_cnt, 1u)] = cw;
-          if (KML_REG_QUEUE_EARLY) red[3] = (int)atomicAdd(queue, 1u);  // (every thread has read red[3])
+          red[3] = (int)atomicAdd(queue, 1u);  // (every thread has read red[3])
         }
         continue;
       }
@@ -646,8 +540,8 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
     }
 
     REG_STAMP(3);
-    unsigned nxt = 0;  // KML_REG_QUEUE_EARLY: the next entry, in flight through the epilogue
-    if (KML_REG_QUEUE_EARLY && tid == 0) nxt = atomicAdd(queue, 1u);
+    unsigned nxt = 0;  // the next entry, in flight through the epilogue
+    if (tid == 0) nxt = atomicAdd(queue, 1u);
 #if KML_STAMPS
     if (tid == 0) {
       rs_acc[6] += 1;
@@ -679,13 +573,12 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
         if (cnt) atomicAdd(&red[0], cnt);
       }
       if (a.ref_bits) {  // CntErr (sourcesink.cc:29-47): two 64-bit words per wave and round, loads first
-        const uint64_t *ref = a.ref_bits + (long long)cw * c.Kw;  // (KML_REG_EPI_LDS = 0)
         const int lane = tid & 63;
         int errs = 0;
         for (int w0 = tid >> 6; w0 < c.Kw; w0 += 2 * (T / 64)) {
           const int w1 = w0 + T / 64;
-          const uint64_t r0 = KML_REG_EPI_LDS ? refw[w0] : ref[w0];
-          const uint64_t r1 = w1 < c.Kw ? (KML_REG_EPI_LDS ? refw[w1] : ref[w1]) : 0ull;
+          const uint64_t r0 = refw[w0];
+          const uint64_t r1 = w1 < c.Kw ? refw[w1] : 0ull;
           const int i0 = w0 * 64 + lane, i1 = w1 * 64 + lane;
           const int b0 = i0 < c.K ? cch[ipos[i0]] : 0;
           const int b1 = i1 < c.K && w1 < c.Kw ? cch[ipos[i1]] : 0;
@@ -702,29 +595,27 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
       if (a.parity_cnt) a.parity_cnt[cw] = red[0];
       if (a.cw_err && a.ref_bits) a.cw_err[cw] = a.iter_count > 0 ? red[1] : 0;
       if (a.iters) a.iters[cw] = iter;
-      if (a.counters) {
-        unsigned long long *ct = cnt_lds ? wcnt : a.counters;  // (LDS: flushed at the exit)
+      if (a.counters) {  // (summed in LDS: flushed at the exit)
         const unsigned long long vn = conv ? (unsigned long long)iter + 1 : (unsigned long long)iter;
-        atomicAdd(&ct[CNT_VN_PHASES], vn);
-        atomicAdd(&ct[CNT_CN_PHASES], (unsigned long long)iter);
-        if (conv) atomicAdd(&ct[CNT_CONVERGED], 1ull);
+        atomicAdd(&wcnt[CNT_VN_PHASES], vn);
+        atomicAdd(&wcnt[CNT_CN_PHASES], (unsigned long long)iter);
+        if (conv) atomicAdd(&wcnt[CNT_CONVERGED], 1ull);
         if (a.ref_bits && a.iter_count > 0) {
           const int errs = red[1];
-          atomicAdd(&ct[CNT_ERR_BIT], (unsigned long long)errs);
-          atomicAdd(&ct[CNT_ERR_BLK], errs > 0 ? 1ull : 0ull);
-          atomicAdd(&ct[CNT_TOT_BIT], (unsigned long long)c.K);
-          atomicAdd(&ct[CNT_TOT_BLK], 1ull);
+          atomicAdd(&wcnt[CNT_ERR_BIT], (unsigned long long)errs);
+          atomicAdd(&wcnt[CNT_ERR_BLK], errs > 0 ? 1ull : 0ull);
+          atomicAdd(&wcnt[CNT_TOT_BIT], (unsigned long long)c.K);
+          atomicAdd(&wcnt[CNT_TOT_BLK], 1ull);
         }
       }
-      if (KML_REG_QUEUE_EARLY) {  // after the reads above; read by all after the loop's barrier
-        red[3] = (int)nxt;
-        red[0] = 0;
-        red[1] = 0;
-      }
+      // after the reads above; read by all after the loop's barrier
+      red[3] = (int)nxt;
+      red[0] = 0;
+      red[1] = 0;
     }
     REG_STAMP(5);
   }
-  if (cnt_lds && tid == 0)  // the workgroup's sums (only thread 0 wrote them)
+  if (a.counters && tid == 0)  // the workgroup's sums (only thread 0 wrote them)
     for (int i = 0; i <= CNT_CONVERGED; ++i)
       if (wcnt[i]) atomicAdd(&a.counters[i], wcnt[i]);
 #if KML_STAMPS

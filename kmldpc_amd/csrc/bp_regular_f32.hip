@@ -152,10 +152,10 @@ __global__ __launch_bounds__(T) void bp_regular_f32_kernel(DevCode c, BpLaunch a
         const double2 v = yy[j];
         double out[DMB];
         if constexpr (EXACT)
-          demap_symbol_t<DMB, false, lds_cons, 2, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x, hh.y,
+          demap_symbol_t<DMB, false, lds_cons, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x, hh.y,
                                                           a.sym_var, out);
         else
-          dok &= demap_symbol_t<DMB, true, lds_cons, 2, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x,
+          dok &= demap_symbol_t<DMB, true, lds_cons, false>((lds_cons)dcons, (lds_exptab)detab, v.x, v.y, hh.x,
                                                               hh.y, a.sym_var, out);
 #pragma unroll
         for (int b = 0; b < DMB; ++b) p0s[j * DMB + b] = flt2{(float)out[b], (float)(1.0 - out[b])};

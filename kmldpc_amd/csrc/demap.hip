@@ -35,34 +35,23 @@ namespace {
 // EXACT: the listed symbols on the exact path (div_rn, kml_exp), or, when the
 // list overflowed, every symbol carrying the sentinel.
 // 64QAM: the 64 probabilities of a symbol stay in registers (280 VGPRs
-// unconstrained, one wave per SIMD); KML_DEMAP64_WAVES caps the kernel so that
-// several waves per SIMD hide the exp table loads and the dependent chains
-// (A/B) 1: the 64QAM demap_kernel reads bank-private copies of the exp table
-// (demap_common.hpp stage_exp_table_banked).  Measured: 0.89 ms per 4096
-// PEG8064 codewords against 0.87 with the plain table (profiles/r04_ab2_summary.txt):
-// the bank conflicts were not on the kernel's critical path.
-#ifndef KML_EXPTAB_BANKED
-#define KML_EXPTAB_BANKED 0
-#endif
+// unconstrained, one wave per SIMD); kDemap64Waves caps the kernel so that
+// several waves per SIMD hide the exp table loads and the dependent chains.
+// Bank-private copies of the exp table for the 64QAM demap_kernel measured
+// 0.89 ms per 4096 PEG8064 codewords against 0.87 with the plain table
+// (profiles/r04_ab2_summary.txt): the bank conflicts were not on the kernel's
+// critical path.
 // Round 4: 64QAM at 3 waves per SIMD (168 VGPRs: 37 spilled, as many as at
 // 256), 16QAM at 4 (128 VGPRs, 2 spilled): 0.87 -> 0.84 ms and 0.295 -> 0.291
 // ms per 4096 PEG8064 / 16384 BG2 codewords (profiles/r04_ab17_summary.txt)
-#ifndef KML_DEMAP64_WAVES
-#define KML_DEMAP64_WAVES 3
-#endif
-#ifndef KML_DEMAP16_WAVES
-#define KML_DEMAP16_WAVES 4
-#endif
+constexpr int kDemap64Waves = 3, kDemap16Waves = 4;
 template <int MB, bool EXACT, bool ROT = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? KML_DEMAP64_WAVES : MB == 4 ? KML_DEMAP16_WAVES : 1))) void demap_kernel(const double *__restrict__ cons, const double2 *__restrict__ y,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? kDemap64Waves : MB == 4 ? kDemap16Waves : 1))) void demap_kernel(const double *__restrict__ cons, const double2 *__restrict__ y,
                                                     int S, int reps, const double2 *__restrict__ h, int h_stride,
                                                     const int32_t *__restrict__ h_sel, double var, int B,
                                                     double *__restrict__ p0, DemapDefer d) {
   __shared__ double cl[2 << MB];  // the constellation, read with uniform LDS loads
-  // the exp table: bank-private copies for 64QAM (64 exps per symbol), the
-  // plain table otherwise (demap_common.hpp stage_exp_table_banked)
-  constexpr int ES = (MB >= 6 && KML_EXPTAB_BANKED) ? kExpBanked : 2;
-  __shared__ uint64_t etab[ES == 2 ? 256 : 128 * kExpBanked];
+  __shared__ uint64_t etab[256];  // the exp table (demap_common.hpp stage_exp_table)
   // ROT (64QAM, FAST, one symbol per thread, S >= 256: launch_demap): the
   // points times the channel of the (at most two) codewords of this
   // workgroup's symbols, formed once per workgroup instead of once per symbol
@@ -78,10 +67,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? K
     if (listed) todo = cnt;
   }
   for (int k = threadIdx.x; k < (2 << MB); k += blockDim.x) cl[k] = cons[k];
-  if constexpr (ES == 2)
-    stage_exp_table(etab);
-  else
-    stage_exp_table_banked(etab);
+  stage_exp_table(etab);
   const int ent0 = (int)((long long)blockIdx.x * blockDim.x / S);
   if (ROT)
     for (int t = threadIdx.x; t < (2 << MB); t += blockDim.x) {
@@ -93,7 +79,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? K
       crot[2 * t + 1] = cr * hh.y + ci * hh.x;
     }
   __syncthreads();
-  const lds_exptab et = (lds_exptab)etab + (ES == 2 ? 0 : 2 * (threadIdx.x & 15));
+  const lds_exptab et = (lds_exptab)etab;
   // grid-stride over the symbols: the LDS staging above is paid once per
   // workgroup, not once per 256 symbols
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < todo; i += (long long)gridDim.x * blockDim.x) {
@@ -108,10 +94,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? K
     if constexpr (EXACT)
       demap_symbol_t<MB, false>((lds_cons)cl, (lds_exptab)etab, yy.x, yy.y, hh.x, hh.y, var, out);
     else if (ROT)
-      ok = demap_symbol_t<MB, true, lds_cons, ES, true, ROT>((lds_cons)crot + ((ent - ent0) << (MB + 1)), et, yy.x,
+      ok = demap_symbol_t<MB, true, lds_cons, true, ROT>((lds_cons)crot + ((ent - ent0) << (MB + 1)), et, yy.x,
                                                               yy.y, hh.x, hh.y, var, out);
     else
-      ok = demap_symbol_t<MB, true, lds_cons, ES>((lds_cons)cl, et, yy.x, yy.y, hh.x, hh.y, var, out);
+      ok = demap_symbol_t<MB, true, lds_cons>((lds_cons)cl, et, yy.x, yy.y, hh.x, hh.y, var, out);
     // stored unconditionally: an unproven symbol gets the sentinel p0 = -1 in
     // its first bit (a P0 is in [1e-12, 1 - 1e-12]) and the EXACT instance
     // rewrites all its bits; no branch around the stores, so the outputs are
@@ -210,10 +196,7 @@ __device__ __forceinline__ bool cand_metric_cw(int cw, const DevCode &c, const d
   if (!EXACT && cnt[5]) return false;  // uniform: every thread read the flag after the barrier
   int local[4] = {0, 0, 0, 0};
   const unsigned *hb32 = reinterpret_cast<const unsigned *>(hb);
-#ifndef KML_CM_ROW6  // (A/B) 0: the generic row loop
-#define KML_CM_ROW6 1
-#endif
-  if (KML_CM_ROW6 && c.regular && c.dc_max == 6) {  // (PEG codes) row r's edges at 6 r: three independent 8-byte loads
+  if (c.regular && c.dc_max == 6) {  // (PEG codes) row r's edges at 6 r: three independent 8-byte loads
     for (int r = tid; r < c.M; r += blockDim.x) {
       const int2 *rc = reinterpret_cast<const int2 *>(c.row_col + 6 * r);  // 8-byte aligned (256-aligned base)
       const int2 e0 = rc[0], e1 = rc[1], e2 = rc[2];
@@ -254,13 +237,7 @@ template <int MB, bool EXACT>
 // 0.73; profiles/r04_ab9_summary.txt); 64QAM 4 (128 VGPRs: the 64 screen terms
 // fit, the spills sit in the undecided list's exact demap): 0.73 -> 0.70 ms per
 // 4096 PEG8064 codewords against 3 (r04_ab10_summary.txt).
-#ifndef KML_CM_SMALL_WAVES
-#define KML_CM_SMALL_WAVES 8
-#endif
-#ifndef KML_CM_BIG_WAVES
-#define KML_CM_BIG_WAVES 4
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? KML_CM_BIG_WAVES : MB <= 2 ? KML_CM_SMALL_WAVES : 1))) void cand_metric_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MB >= 6 ? 4 : MB <= 2 ? 8 : 1))) void cand_metric_kernel(
     DevCode c, const double *__restrict__ cons, const double2 *__restrict__ y, int S, const double2 *__restrict__ h4,
     int nc, double var, double inv_var, double *__restrict__ metrics, int32_t *__restrict__ chosen, DemapDefer d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -36,20 +36,6 @@ typedef const __attribute__((address_space(3))) uint64_t *lds_exptab;
 __device__ __forceinline__ void stage_exp_table(uint64_t *dst) {  // dst: a __shared__ array
   for (int i = threadIdx.x; i < 256; i += blockDim.x) dst[i] = kExpTabDev[i];
 }
-// Bank-private form (ES = kExpBanked u64 per entry): 16 copies of the table,
-// entry i of copy L at byte 256 i + 16 L, and lane L (mod 16) reads copy L
-// (the base pointer it passes is dst + 2 (lane & 15)).  A ds_read_b128 is
-// serviced 16 lanes per pass, one 4-bank group per lane, so the random table
-// indices of a wave's exps no longer collide on banks (32 KB of LDS; the
-// 64QAM demap_kernel).
-constexpr int kExpBanked = 32;
-__device__ __forceinline__ void stage_exp_table_banked(uint64_t *dst) {  // dst: a __shared__ array of 4096
-  for (int i = threadIdx.x; i < 128 * 16; i += blockDim.x) {
-    const int e = i >> 4, L = i & 15;
-    dst[e * kExpBanked + 2 * L] = kExpTabDev[2 * e];
-    dst[e * kExpBanked + 2 * L + 1] = kExpTabDev[2 * e + 1];
-  }
-}
 
 // glibc's exp (kml_exp_t<true>) on its main path only: exact for x == 0 and
 // for 2^-54 <= |x| < 512, where glibc takes no special case (x == 0 gives
@@ -59,7 +45,6 @@ __device__ __forceinline__ bool exp_core_ok(double x) {
   const double a = fabs(x);  // branch-free: (2^-54 <= |x| < 512) or x == 0
   return ((a >= 0x1p-54) & (a < 512.0)) | (x == 0.0);
 }
-template <int ES = 2>  // u64 per table entry: 2 (stage_exp_table) or kExpBanked
 __device__ __forceinline__ double exp_core(double x, lds_exptab tab) {
   const double InvLn2N = 0x1.71547652b82fep0 * 128;
   const double Shift = 0x1.8p52;
@@ -71,7 +56,7 @@ __device__ __forceinline__ double exp_core(double x, lds_exptab tab) {
   const uint64_t ki = as_u64(kd);
   kd -= Shift;
   const double r = fma(kd, NegLn2loN, fma(kd, NegLn2hiN, x));
-  const int idx = (int)(ES * (ki % 128));
+  const int idx = (int)(2 * (ki % 128));
   const double tail = as_f64(tab[idx]);
   const uint64_t sbits = tab[idx + 1] + (ki << (52 - 7));
   const double r2 = r * r;
@@ -103,10 +88,7 @@ __device__ __forceinline__ double exp_core(double x, lds_exptab tab) {
 // (cr hr - ci hi, cr hi + ci hr) in the reference's operation order
 // (demap_kernel stages them per codeword), and hr, hi are unused: the same
 // values, 6 fewer operations per point.
-#ifndef KML_DEMAP_MX_NMIN  // (A/B) 0: the running maximum of the reference's loop
-#define KML_DEMAP_MX_NMIN 1
-#endif
-template <int MB, bool FAST, class CP, int ES = 2, bool LEAN = true, bool ROT = false>
+template <int MB, bool FAST, class CP, bool LEAN = true, bool ROT = false>
 __device__ __forceinline__ bool demap_symbol_t(CP cons, lds_exptab etab, double yr, double yi, double hr,
                                                double hi, double var, double *out) {
   static_assert(!ROT || FAST, "pre-rotated points: FAST path only");
@@ -137,13 +119,13 @@ __device__ __forceinline__ bool demap_symbol_t(CP cons, lds_exptab etab, double 
       d = div_rn(n, var);
     }
     pr[k] = -d;
-    if (!(FAST && KML_DEMAP_MX_NMIN) && (k == 0 || mx < pr[k])) mx = pr[k];  // *max_element
+    if (!FAST && (k == 0 || mx < pr[k])) mx = pr[k];  // *max_element
   }
   // FAST: *max_element = -RN(nmin / var): every d_k = RN(n_k / var) once the
   // proofs pass, and RN(x / var) is non-decreasing in x (var > 0), so the
   // largest -d_k is -RN(min n_k / var), proven like the others (no
   // per-point running maximum)
-  if (FAST && KML_DEMAP_MX_NMIN) mx = -qdiv(nmin, var, rv, dok);
+  if (FAST) mx = -qdiv(nmin, var, rv, dok);
   if (FAST && !(dok && nmin >= 0x1p-512 && nmax <= 0x1p512 && var >= 0x1p-64 && var <= 0x1p64)) return false;
   double sum = 0.0;
   bool eok = true;
@@ -152,7 +134,7 @@ __device__ __forceinline__ bool demap_symbol_t(CP cons, lds_exptab etab, double 
     const double x = pr[k] - mx;
     if (FAST) {  // glibc's main path (exp_core), the rest falls back
       eok &= exp_core_ok(x);
-      pr[k] = exp_core<ES>(x, etab);
+      pr[k] = exp_core(x, etab);
     } else {
       pr[k] = kml_exp(x);  // glibc exp, bit-exact (exact_math.hpp)
     }
@@ -292,10 +274,7 @@ __device__ __forceinline__ bool hard_bits_screen(CP cons, CP scr, double cbound,
   // sums ordered the other way, where the smaller-labelled sum is at least
   // total / 2, so the extra error stays below 2^-17 relative to the sums
   // compared, far inside the 2^-12 margin.
-#ifndef KML_SCREEN_COMPLEMENT
-#define KML_SCREEN_COMPLEMENT 1
-#endif
-  constexpr bool kComplement = KML_SCREEN_COMPLEMENT && MB >= 4;
+  constexpr bool kComplement = MB >= 4;
   float tot = 0.f;
 #pragma unroll
   for (int k = 0; k < KC; ++k) {

@@ -12,23 +12,21 @@
 // 1. dd_quot + dd_check (the decoders' FAST VN divisions, demap_common.hpp):
 //    y0 = v_rcp_f64(s), whose relative error e0 the ISA documents as at most
 //    2^29 ulp = 2^-23 (tests/test_gpu_parity.py::test_hardware_reciprocal_error
-//    measures it on the device).  Shipped form (KML_DD_NEWTON = 1): one Newton
+//    measures it on the device).  One Newton
 //    step y1 = y0 + y0 RN(1 - s y0), e1 = RN(1 - s y1) (fma), |e1| <= e0^2 +
 //    2^-53 < 2^-45, hi = y1, ylo = RN(e1 y1), yk = RN(y1 (1 + 2^-40)).
-//    y1 + e1 y1 = (1 - e1^2) / s.  Alternative (KML_DD_NEWTON = 0, one
+//    y1 + e1 y1 = (1 - e1^2) / s.  (A Newton-free form, hi = y0, e = RN(1 - s y0),
+//    ylo = RN(y0 RN(e + e^2)), yk = RN(y0 (1 + 2^-40) + ylo), is one
 //    instruction less per pair but measured 2.7 % slower on the headline BP
-//    kernel: its yk waits on ylo): hi = y0, e = RN(1 - s y0),
-//    ylo = RN(y0 RN(e + e^2)), yk = RN(y0 (1 + 2^-40) + ylo); y0 (1 + e* + e*^2)
-//    = (1 - e*^3) / s.  Either way y0 + ylo (resp. y1 + ylo) is within 2^-67 of
-//    1/s, and
+//    kernel: its yk waits on ylo; DESIGN.md keeps the measurement.)
+//    y1 + ylo is within 2^-67 of 1/s, and
 //        q = fma(n, hi, RN(n ylo))
 //    rounds a value within 2^-66 relative of n/s once: q is a FAITHFUL
 //    rounding of n/s (one of its two neighbours).  Premise: e0 <= 2^-23 (the
 //    ISA's bound, which test_hardware_reciprocal_error asserts on the device
 //    and tests/test_division_model.py replays adversarially as +-2^-23 in
-//    exact rational arithmetic, both forms).  The argument itself has slack:
-//    the Newton form needs e0 <= 2^-20.1 (F > 1 below needs |e1| < 2^-40.2),
-//    the Newton-free form e0 <= 2^-22.3 (its e*^3 <= 2^-67).
+//    exact rational arithmetic).  The argument itself has slack:
+//    it needs e0 <= 2^-20.1 (F > 1 below needs |e1| < 2^-40.2).
 //    The check: r = fma(-q, s, n) is exact (q faithful; n = 0 or n >= 2^-969,
 //    s and q normal), r = s (n/s - q).  With yk as above,
 //        t = fma(r, yk, q) = RN(q + (n/s - q) F),  F = s yk = (1 + d)(1 + 2^-40) + eps',
@@ -46,8 +44,8 @@
 //    with dd_fix (q faithful: RN(n/s) is q or its neighbour, told apart by
 //    their exact residuals) instead of redoing the codeword; the demapper
 //    reruns the symbol on the exact path.
-//    Cost per normalisation pair: v_rcp_f64 + 5 shared (4 without the Newton
-//    step) + 5 per quotient (+ the fix, rare).
+//    Cost per normalisation pair: v_rcp_f64 + 5 shared + 5 per quotient (+ the
+//    fix, rare).
 //
 // 2. div_rn (every other division: the decoders' exact re-decode, the
 //    non-FAST demap, k-means): any operands.  Finite normal operands with
@@ -68,28 +66,17 @@
 namespace kml {
 
 // The double-double reciprocal and the proof's scaled reciprocal:
-//   KML_DD_NEWTON = 1 (shipped): hi = y1 = y0 + y0 RN(1 - s y0), lo = RN(e1 y1)
-//                                with e1 = RN(1 - s y1), k = RN(y1 (1 + 2^-40));
-//   KML_DD_NEWTON = 0:           hi = y0, lo = RN(y0 RN(e + e^2)) with
-//                                e = RN(1 - s y0), k = RN(y0 (1 + 2^-40) + lo).
+// hi = y1 = y0 + y0 RN(1 - s y0), lo = RN(e1 y1) with e1 = RN(1 - s y1),
+// k = RN(y1 (1 + 2^-40)).
 struct DdRcp {
   double hi, lo, k;
 };
 
-#ifndef KML_DD_NEWTON
-#define KML_DD_NEWTON 1
-#endif
 __device__ __forceinline__ DdRcp dd_rcp(double s) {
   const double y0 = __builtin_amdgcn_rcp(s);
-#if KML_DD_NEWTON  // (A/B) round 3's first form: one Newton step, y1 + RN(e1 y1), yk = RN(y1 (1 + 2^-40))
   const double y1 = fma(y0, fma(-y0, s, 1.0), y0);
   const double e1 = fma(-y1, s, 1.0);
   return {y1, e1 * y1, y1 * (1.0 + 0x1p-40)};
-#else
-  const double e = fma(-y0, s, 1.0);
-  const double lo = y0 * fma(e, e, e);
-  return {y0, lo, fma(y0, 1.0 + 0x1p-40, lo)};
-#endif
 }
 
 __device__ __forceinline__ double dd_quot(double n, const DdRcp &y) { return fma(n, y.hi, n * y.lo); }

@@ -373,10 +373,7 @@ __device__ __forceinline__ float wave_min_f(float v) {
 // elements per lane per step: 5 covers a QPSK cluster-0 list (~286) in one
 // step; measured per 32768 PEG2304/QPSK codewords: 4 -> 3.42 ms, 5 -> 3.31 ms,
 // 8 -> 3.89 ms (longer in-lane chains and registers)
-#ifndef KML_KM_SCAN_PER
-#define KML_KM_SCAN_PER 5
-#endif
-constexpr int kScanPer = KML_KM_SCAN_PER;
+constexpr int kScanPer = 5;
 constexpr double kScanMargin = 64.0;      // grid steps kept from the binade ends: room for the tie corrections
 constexpr int kScanMaxTies = 32;          // ties resolved in one step (each moves later prefixes by <= 1)
 template <int CTRL, int ROWS>
@@ -578,16 +575,8 @@ __device__ __forceinline__ double norm2_up(double a, double b) {
 
 // the tie-band / exact decision out of line (rare; keeps the hot loop's
 // registers free)
-#ifndef KML_KM_OUTLINE
-#define KML_KM_OUTLINE 1
-#endif
-#if KML_KM_OUTLINE
-#define KM_SLOW __noinline__
-#else
-#define KM_SLOW __forceinline__
-#endif
 template <int KC>
-__device__ KM_SLOW bool member0_slow(const double2 *cl, double yr, double yi) {
+__device__ __noinline__ bool member0_slow(const double2 *cl, double yr, double yi) {
   return member0<KC>(cl, yr, yi);
 }
 
@@ -630,7 +619,7 @@ __device__ __forceinline__ bool screen0(const double2 *cl, double yr, double yi,
   return hmin > kD2HiLo && hmax < kD2HiHi && (in || out);
 }
 
-__device__ KM_SLOW cplx cdiv_slow(cplx n, cplx dd) { return kml_cdiv(n, dd); }
+__device__ __noinline__ cplx cdiv_slow(cplx n, cplx dd) { return kml_cdiv(n, dd); }
 
 // A symbol's drift threshold D + g / (2 Cmax), rounded down: the (1 - 2^-20)
 // factor covers the float conversion's rounding in the normal range; below
@@ -642,20 +631,14 @@ __device__ __forceinline__ float km_threshold(double drift, double g, double inv
   return td < 0x1p-126 ? 0.0f : td < 0x1p127 ? (float)td : 0x1p127f;
 }
 
-// Threshold tiers of the incremental assignment (KML_KM_WEAK): a word's few
+// Threshold tiers of the incremental assignment: a word's few
 // symbols closest to a decision boundary (the kKmWeak smallest thresholds) are
 // re-assigned on their own, gathered from several words into one pass, while
 // the drift stays below the word's other thresholds; the whole word is
 // re-assigned only when it reaches those.  A CPU model of the rule
 // (PEG2304 / QPSK, 2 dB) re-assigns 2.6 instead of 6.2 whole words per
 // iteration, plus ~10 weak symbols in one gathered pass.
-#ifndef KML_KM_WEAK
-#define KML_KM_WEAK 1
-#endif
-#ifndef KML_KM_WEAK_K  // weak symbols per word (<= 4: packed 7-bit lane indices)
-#define KML_KM_WEAK_K 3
-#endif
-constexpr int kKmWeak = KML_KM_WEAK_K;
+constexpr int kKmWeak = 3;  // weak symbols per word (<= 4: packed 7-bit lane indices)
 
 // kml_cdiv(n, {c, 0}) for a count c >= 1: __divdc3's |c| >= |d| branch with
 // ratio = 0 / c = 0 and denom = 0 * 0 + c = c, where fabs(ratio) > DBL_MIN is
@@ -723,7 +706,7 @@ __device__ __forceinline__ cplx cdiv_const(cplx n, cplx dd, const CdivConst &k) 
 // per SIMD) and there is no workgroup barrier at all.  The real and the
 // imaginary chains are summed by the same wave one after the other (both in
 // one scan step measured slower: more registers).
-// Member list in per-word segments (KML_KM_SEG): word w's members in
+// Member list in per-word segments (kSeg): word w's members in
 // ascending order, then -0.0 fillers up to its capacity (members at the last
 // layout + kKmSlack).  x + (-0.0) == x for every x (signed zeros, infinities
 // and NaNs included), so the ordered sum over the list equals the sum over the
@@ -733,35 +716,18 @@ __device__ __forceinline__ cplx cdiv_const(cplx n, cplx dd, const CdivConst &k) 
 // scanned elements, tools/probe/km_seg_model.py; measured 2.41 -> 2.28 ms per
 // 32,768 blind PEG2304 codewords, slack 2: 2.39 ms — the list passes 320
 // elements, one scan step).
-#ifndef KML_KM_SEG
-#define KML_KM_SEG 1
-#endif
-#ifndef KML_KM_SLACK
-#define KML_KM_SLACK 1
-#endif
-constexpr int kKmSlack = KML_KM_SLACK;
-#ifndef KML_KM_WAVE_OCC
-#define KML_KM_WAVE_OCC 6  // waves per SIMD (registers <= 512 / OCC): 6 (80 VGPRs, 9 spilled) 2.75 ms, 5 3.04, 4 3.31
-#endif
-#ifndef KML_KM_CAPMUL  // member-list capacity S * CAPMUL / CAPDIV (A/B with the occupancy)
-#define KML_KM_CAPMUL 1
-#endif
-#ifndef KML_KM_CAPDIV
-#define KML_KM_CAPDIV 3
-#endif
+constexpr int kKmSlack = 1;
+constexpr int kKmWaveOcc = 6;  // waves per SIMD (registers <= 512 / OCC): 6 (80 VGPRs, 9 spilled) 2.75 ms, 5 3.04, 4 3.31
 // Codewords (waves) per workgroup.  One: a workgroup's LDS is released when its
 // own codeword ends, not with the slowest of four (iteration counts vary), and
 // the dispatcher refills the CU per codeword: blind PEG2304 2.69 ms with four,
 // 2.59 with two, 2.44 with one (profiles/r05_ab5_summary.txt).
-#ifndef KML_KM_WPG
-#define KML_KM_WPG 1
-#endif
-constexpr int kWaveWpg = KML_KM_WPG;
+constexpr int kWaveWpg = 1;
 struct KmWaveLds {
   int cap, off_cl, stride;
 };
 __host__ __device__ constexpr KmWaveLds km_wave_lds(int S, int KC) {
-  const int cap = ((S * KML_KM_CAPMUL + KML_KM_CAPDIV - 1) / KML_KM_CAPDIV + 7) & ~7;  // (A/B) larger clusters: the fallback sum
+  const int cap = ((S + 2) / 3 + 7) & ~7;  // a third of the symbols; larger clusters: the fallback sum
   const int off_cl = 16 * cap;
   // then the cluster points [KC], the constellation [KC] and the launch
   // constants (KmWaveConst): kept in LDS, not in registers across the loop
@@ -773,7 +739,7 @@ struct KmWaveConst {
 };
 
 template <int KC>
-__global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(KML_KM_WAVE_OCC))) void km_wave_kernel(
+__global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(kKmWaveOcc))) void km_wave_kernel(
     const double *__restrict__ cons, const double *__restrict__ rot, const double2 *__restrict__ y, int S, int iters,
     int B, double2 *__restrict__ h_hat, double2 *__restrict__ h4, double2 *__restrict__ hat_out, int incremental,
     int scan) {
@@ -793,7 +759,7 @@ __global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(K
   // segments pay off where a word holds many members (QPSK / 4PSK: ~16 of 64);
   // for 16 and 64 points the fillers would lengthen the scanned list by 25 % /
   // 100 % (64QAM measured 0.48 -> 0.49 ms), so those keep the compacted list
-  constexpr bool kSeg = KML_KM_SEG && KC <= 4;
+  constexpr bool kSeg = KC <= 4;
 #if KML_STAMPS
   unsigned long long km_prev = __builtin_amdgcn_s_memtime();
   unsigned long long km_acc[KS_WEAK + 1] = {};
@@ -887,12 +853,10 @@ __global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(K
   // lane w < Sw: word w's membership bits and its threshold min(D(ref) + g / (2 Cmax)); -1: assign
   uint64_t wb = 0;
   float wt = -1.0f;
-#if KML_KM_WEAK
-  // tiers (KML_KM_WEAK): wt is the minimum threshold of the word's kKmWeak weak
+  // tiers: wt is the minimum threshold of the word's kKmWeak weak
   // symbols (packed 7-bit lane indices in wk, bit 6 = none), wt2 that of the others
   float wt2 = -1.0f;
   unsigned wk = 0;
-#endif
   uint64_t wb_list = 0;  // lane w: word w's bits and list offset at the last rebuild
   // kSeg: lane w: word w's segment of the value list, offset << 16 | capacity
   // (members + kKmSlack -0.0 fillers, at most 64); nlist: the list's length
@@ -929,7 +893,6 @@ __global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(K
     // assignment (kmeans.cc:36-46) of the words whose decisions the drift may
     // have changed; two words per pass (independent loads, screens and minima)
     int chg = 0;
-#if KML_KM_WEAK
     {
       // a full pass over the words whose other symbols' thresholds the drift
       // reached; a gathered pass over the weak symbols of the words where only
@@ -1017,39 +980,6 @@ __global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(K
         KM_COUNT(KS_WORDS, 1);
       }
     }
-#else
-    {
-      uint64_t need = __ballot(lane < Sw && (!incremental || !(drift < (double)wt)));
-      while (need) {  // wave-uniform, one flagged word per pass
-        const int q = __builtin_ctzll(need);
-        need &= need - 1;
-        const double2 v = yy[min(q * 64 + lane, S - 1)];
-        const bool valid = q * 64 + lane < S;
-        bool m;
-        double g;
-        const bool dec = screen0<KC>(cl, v.x, v.y, m, g);
-        if (__ballot(valid && !dec))
-          if (valid && !dec) {  // tie band / range: the exact decision
-            m = member0_slow<KC>(cl, v.x, v.y);
-            g = 0.0;
-          }
-        // D + g / (2 Cmax), rounded down: the (1 - 2^-20) factor covers the
-        // float conversion's rounding in the normal range; below FLT_MIN (where
-        // a denormal's relative rounding error is unbounded) the threshold is 0,
-        // i.e. the word is re-assigned next iteration; past the float range a
-        // finite 2^127
-        const double td = (drift + g * kc->inv2c) * (1.0 - 0x1p-20);
-        const float t = wave_min_f(valid ? (td < 0x1p-126 ? 0.0f : td < 0x1p127 ? (float)td : 0x1p127f) : INFINITY);
-        const uint64_t bits = __ballot(valid && m);
-        if (it == 0 || bits != lane_u64(wb, q)) chg = 1;
-        if (lane == q) {
-          wb = bits;
-          wt = t;
-        }
-        KM_COUNT(KS_WORDS, 1);
-      }
-    }
-#endif
     KM_STAMP(KS_ASSIGN);
     if (kSeg && chg) {  // members changed: rewrite the changed words' segments (coalesced loads, lanes = symbols)
       KM_COUNT(KS_COMPACTIONS, 1);

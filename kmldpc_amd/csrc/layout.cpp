@@ -442,10 +442,6 @@ struct PartRefiner {
   }
 };
 
-#ifndef KML_PART_ANNEAL  // (A/B) 0: members' columns in index order
-#define KML_PART_ANNEAL 1
-#endif
-
 static bool plan_partition_uncached(const LdpcCode &L, int G, PartitionPlan &out);
 
 // Cached like plan_regular_layout: a pure function of the graph, and the
@@ -649,8 +645,7 @@ static bool plan_partition_uncached(const LdpcCode &L, int G, PartitionPlan &out
   // receive, interior columns first, measured slower: 8.75 vs 8.20 ms per 4096
   // PEG8064 codewords, profiles/r05_ab2_summary.txt)
   std::vector<int> nbound(G, NG);
-  const char *il_env = getenv("KML_PART_INTERIOR_LAST");  // (A/B) 0: columns in index order
-  for (int g = 0; g < G && !(il_env && il_env[0] == '0'); g++) {
+  for (int g = 0; g < G; g++) {
     auto interior = [&](int j) {
       for (int e = L.col_ptr[j]; e < L.col_ptr[j + 1]; e++)
         if (best_r[col_rows[e]] != g) return false;
@@ -661,7 +656,7 @@ static bool plan_partition_uncached(const LdpcCode &L, int G, PartitionPlan &out
   }
   out.interior = 0;
   for (int g = 0; g < G; g++) out.interior += NG - nbound[g];
-  if (KML_PART_ANNEAL) {
+  {
     std::vector<uint8_t> wb((size_t)N * dv), rb((size_t)N * dv);
     for (int j = 0; j < N; j++)
       for (int k = 0; k < dv; k++) {
@@ -706,10 +701,6 @@ namespace kml {
 namespace {
 
 // One wave's worth of items (64 columns, or 32 rows) for one round.
-#ifndef KML_IRR_PARTIAL_PAIRS
-#define KML_IRR_PARTIAL_PAIRS 1
-#endif
-
 struct WaveItems {
   std::vector<int32_t> a, b;  // a: the (first) items; b: the second items of a pair wave
   double cost = 0;
@@ -735,17 +726,16 @@ bool plan_rounds(std::vector<std::vector<int32_t>> items, int per_wave, int W, i
   // leftover pair slots take a partial pair wave of one degree (at least half
   // a wave of pairs, lowest degrees first), so that fewer single waves mix
   // two degrees (a mixed wave runs both degrees' code paths)
-  if (KML_IRR_PARTIAL_PAIRS)
-    for (int d = 0; d <= std::min(dmax, pair_max) && (int)pairs.size() < W; ++d) {
-      const int np = (int)items[d].size() / 2;
-      if (np < per_wave / 2 || np >= per_wave) continue;
-      WaveItems w;
-      w.a.assign(items[d].begin(), items[d].begin() + np);
-      w.b.assign(items[d].begin() + np, items[d].begin() + 2 * np);
-      items[d].erase(items[d].begin(), items[d].begin() + 2 * np);
-      w.cost = 2 * np * cost(d);
-      pairs.push_back(std::move(w));
-    }
+  for (int d = 0; d <= std::min(dmax, pair_max) && (int)pairs.size() < W; ++d) {
+    const int np = (int)items[d].size() / 2;
+    if (np < per_wave / 2 || np >= per_wave) continue;
+    WaveItems w;
+    w.a.assign(items[d].begin(), items[d].begin() + np);
+    w.b.assign(items[d].begin() + np, items[d].begin() + 2 * np);
+    items[d].erase(items[d].begin(), items[d].begin() + 2 * np);
+    w.cost = 2 * np * cost(d);
+    pairs.push_back(std::move(w));
+  }
   // the rest as single waves, highest degree first; a partial wave is topped up
   // with the next degree's items (a mixed wave)
   WaveItems cur;
@@ -792,10 +782,7 @@ void place_waves(const std::vector<WaveItems> &pairs, const std::vector<WaveItem
 
 // div2 steps of a column (forward d-1, backward 2d-1); a degree-1 column's
 // FAST v2c needs none (bp_irregular.hip vn_cols), only its hard decision
-#ifndef KML_IRR_VN_COST1
-#define KML_IRR_VN_COST1 2.0
-#endif
-double vn_cost(int d) { return d == 1 ? KML_IRR_VN_COST1 : 3.0 * d - 1.0; }
+double vn_cost(int d) { return d == 1 ? 2.0 : 3.0 * d - 1.0; }
 double cn_cost(int d) { return 1.5 * d; }        // per half-row: advances + half the c2v outputs
 
 }  // namespace

@@ -28,7 +28,7 @@ def mul(a, b):
     return rn(F(a) * F(b))
 
 
-NEWTON = True  # the shipped form (exact_div.hpp KML_DD_NEWTON); False: the Newton-free form
+NEWTON = True  # the shipped form (exact_div.hpp dd_rcp); False: the Newton-free form
 
 
 def model(n, s, rel):

@@ -1,8 +1,8 @@
 """The two BP phases bp_regular_kernel no longer computes (bp_regular.hip):
 the VN phase of iteration 0 in closed form on the FAST path
-(KML_REG_ITER0_CLOSED: every v2c is the prior pair, tests/test_iter0_model.py)
+(every v2c is the prior pair, tests/test_iter0_model.py)
 and the budget's last CN phase reduced to its parity check when no syndromes
-are asked for (KML_REG_LAST_CN_PARITY).  Every output stays the reference's bit
+are asked for.  Every output stays the reference's bit
 for bit: PEG2304 + QPSK (N = 2304 is the only shape this kernel takes) against
 the oracle's BP decode of the same priors and the oracle's receive path, with
 iteration budgets that put the shortcuts in the same, in neighbouring and in

@@ -1,6 +1,6 @@
 """The VN phase of BP iteration 0 is the identity on the prior pair (CPU model).
 
-bp_regular.hip (KML_REG_ITER0_CLOSED) replaces the first VN phase of a FAST
+bp_regular.hip (decode_reg's closed form) replaces the first VN phase of a FAST
 decode by stores of (p, 1 - p): InitMsg sets every c2v to (0.5, 0.5), and for a
 prior in the FAST domain (bp_common.hpp fast_prior_ok: +0, 1, or p and 1 - p
 >= lo = 2^(40 dv - 960)) the reference's column recursion

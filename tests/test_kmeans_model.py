@@ -18,7 +18,7 @@ def test_wave_scan_sum_equals_sequential_sum():
 
 
 def test_segment_fillers_are_the_sum_identity():
-    """kmeans.hip KML_KM_SEG: the member list holds -0.0 fillers between the
+    """kmeans.hip kSeg: the member list holds -0.0 fillers between the
     words' members; x + (-0.0) == x for every double x (signed zeros,
     infinities, NaN payloads), so both the sequential sum and the wave scan
     over the filled list equal the sum over the members alone, bit for bit."""

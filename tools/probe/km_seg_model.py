@@ -2,9 +2,9 @@
 ANALYSIS INFRASTRUCTURE ONLY.  On the reference's k-means trajectories
 (kmeans.cc:15-84) for PEG2304 / QPSK frames it counts, per iteration, the
 64-symbol words whose member values are reloaded into the LDS list:
-  * compacted list (KML_KM_SEG=0): every word whose members or list offset
+  * compacted list (16 points and up): every word whose members or list offset
     changed (a count change shifts every later word);
-  * per-word segments (KML_KM_SEG=1) of capacity members + slack: only the
+  * per-word segments (kSeg: up to 4 points) of capacity members + slack: only the
     changed words, plus a full relayout when a word outgrows its segment;
 and the scanned list length (members + fillers).
 

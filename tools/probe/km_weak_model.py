@@ -8,7 +8,7 @@ many 64-symbol words the drift rule re-assigns whole:
     the smallest threshold D_ref + g / (2 Cmax) of its symbols (g: the margin
     between the symbol's distances to cluster 0 and to the nearest other
     cluster);
-  * K > 0 (KML_KM_WEAK, kKmWeak = 3): the K smallest thresholds are the word's
+  * K > 0 (the kernel's kKmWeak = 3): the K smallest thresholds are the word's
     weak symbols, re-assigned on their own (gathered) when D reaches their
     minimum, and the word is re-assigned whole only when D reaches the minimum
     of the others.
