@@ -29,6 +29,11 @@
  *   kml_count_errors          void SourceSink::CntErr(const int*, const int*, int, int)  lib/lab/include/sourcesink.h:15
  *   kml_sim_*                 the throughput driver: frame generation + receive + counting for one
  *                             SNR point of Simulator::run_blocks (src/simulator.cc:112-168)
+ *   kml_sim_decode_profile    no counterpart: the reference answers "BER / FER at iteration budget k" with
+ *                             one run per [ldpc] max_iter = k.  In BinaryLDPCCodec::Decoder iter_count only
+ *                             bounds the loop (lib/lab/src/binaryldpccodec.cc:175-277; the 5G override
+ *                             likewise), so one decode with budget P holds every budget's answer; this
+ *                             entry point returns all P of them from one receive of the resident batch.
  *
  * Conventions
  *   - Every call returns 0 on success or a negative KML_E* code and never exits
@@ -220,6 +225,25 @@ int kml_sync(kml_ctx *ctx);
  * reference buffer is uninitialised).  counters[8] as kml_sim_decode. */
 int kml_sim_decode_ex(kml_ctx *ctx, double snr, int blind, int histogram, int32_t *cw_err, double *metrics,
                       uint64_t *counters);
+/* The resident batch received once (as kml_sim_decode_ex does, blind or known-H) with the
+ * context's max_iter = P; for every iteration budget k = 1..P what a context created with
+ * [ldpc] max_iter = k would count on the same frames:
+ *   prof[P][3]   = {err_bit, err_blk, converged} at budget k (row k-1); may be NULL
+ *   cw_prof[B][P] = error bits of each codeword at budget k;            may be NULL
+ *   counters[8]  as kml_sim_decode (row P-1 of prof equals its err_bit / err_blk / converged).
+ * A codeword whose parity check first passes at iteration c returns, at budget k, the
+ * decisions of iteration min(k-1, c), and counts as converged when c <= k-1; the kernels
+ * count the info-bit errors of every iteration's decisions while they decode.  Only the
+ * final decode is profiled: the blind path's candidate metrics run as in kml_sim_decode.
+ * An empty resident batch zeroes the outputs and returns 0.
+ * KML_E_UNSUP (kml_last_error names the reason): a host-only context; the f32 mode;
+ * a context with the soft-syndrome metric (metric_type = 1); codes that take
+ * bp_part_kernel (PEG8064) or the generic bp_kernel, KML_BP_KERNEL=generic included;
+ * max_iter > 64.  KML_E_ARG: a NULL context, max_iter < 1.  Nothing is launched by a
+ * refused call and there is no fallback to another kernel.  Profiles for the f32 and the
+ * partitioned kernels are follow-ups; so is a profile truncated by the sweep driver's
+ * stop rule (kml_sweep_point / kml_sim_point are unchanged). */
+int kml_sim_decode_profile(kml_ctx *ctx, double snr, int blind, uint64_t *prof, int32_t *cw_prof, uint64_t *counters);
 
 /* --- simulator driver (Simulator::Simulate / run / run_blocks) ------------ */
 /* The parsed config.toml: f[3] = {minimum_snr, maximum_snr, step_snr};

@@ -122,6 +122,7 @@ def lib():
         "kml_get_sym_str": (None, [P, P, I, I]),
         "kml_ref_frames": (I, [P, P, D, I, P, P, P]),
         "kml_sim_decode_ex": (I, [P, D, I, I, P, P, P]),
+        "kml_sim_decode_profile": (I, [P, D, I, P, P, P]),
         "kml_run_config": (I, [P, P, P]),
         "kml_sweep_point": (I, [C.POINTER(PointCfg), BATCH_FN, P, ALLREDUCE_FN, P, REPORT_FN, P, P]),
         "kml_sim_point": (I, [P, C.POINTER(PointCfg), C.c_uint64, ALLREDUCE_FN, P, REPORT_FN, P, P]),
@@ -361,6 +362,21 @@ class Context:
                   "kml_sim_decode_ex")
         return err, met, dict(zip(["err_bit", "err_blk", "tot_bit", "tot_blk", "vn_phases", "cn_phases",
                                    "converged", "redone"], [int(x) for x in cnt[:8]]))
+
+    def sim_decode_profile(self, snr, blind=False, cw_prof=True):
+        """One receive of the resident batch with max_iter = P, reported for every iteration
+        budget k = 1..P (kml_sim_decode_profile): prof uint64 [P][3] = {err_bit, err_blk,
+        converged} at budget k, cw_prof int32 [B][P] = error bits per codeword at budget k
+        (None with cw_prof=False: the per-codeword rows are not copied back), and the usual
+        counter dict."""
+        B, P = self._sim_B, max(self.max_iter, 0)
+        prof = np.zeros((P, 3), np.uint64)
+        cwp = np.zeros((B, P), np.int32) if cw_prof else None
+        cnt = np.zeros(8, np.uint64)
+        self._chk(lib().kml_sim_decode_profile(self._h, float(snr), int(blind), _p(prof), _p(cwp), _p(cnt)),
+                  "kml_sim_decode_profile")
+        return prof, cwp, dict(zip(["err_bit", "err_blk", "tot_bit", "tot_blk", "vn_phases", "cn_phases",
+                                    "converged", "redone"], [int(x) for x in cnt[:8]]))
 
     def run_config(self):
         """The parsed config.toml ([range], [decoder], [xcodec], [histogram], [ldpc])."""

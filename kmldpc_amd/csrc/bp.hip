@@ -27,6 +27,7 @@
 //
 // Compulsory-traffic accounting is accumulated in the counter
 // block: executed VN and CN phases per launch.
+#include <cstdio>
 #include <cstdlib>
 
 #include "bp_common.hpp"
@@ -306,6 +307,24 @@ int kernel_variant() {
 
 bool bp_uses_lds(const DevCode &c) { return (long long)c.E * 16 + kRedBytes + c.N <= kLdsBytes; }
 
+const char *bp_profile_refusal(const DevCode &c, int iter_count) {
+  if (iter_count > kBpProfMaxIter) return "the iteration profile supports max_iter <= 64";
+  // (the environment is read again here: the dispatch caches its first reading)
+  const char *k = getenv("KML_BP_KERNEL");
+  if (kernel_variant() == 1 || (k && k[0] == 'g'))
+    return "the iteration profile is not available with KML_BP_KERNEL=generic (bp_kernel has no profile mode)";
+  if (!bp_uses_lds(c)) {
+    static thread_local char msg[160];  // (contexts of different threads may ask at once)
+    snprintf(msg, sizeof msg, "the iteration profile is not available for codes that take %s (a follow-up)",
+             bp_coop_groups(c) > 0 ? bp_coop_family(c) : "the generic bp_kernel");
+    return msg;
+  }
+  const bool reg = c.reg_c2v && bp_regular_threads(c.N, c.M, c.E, c.dv_max, c.dc_max, c.regular) == 768;
+  if (!reg && !(c.irr_ok && c.irr_vn))
+    return "the iteration profile is not available for codes that take the generic bp_kernel";
+  return nullptr;
+}
+
 long long bp_gslots_needed(const DevCode &c) {
   if (bp_uses_lds(c)) return 0;
   int dev = 0, ncu = 0;
@@ -326,6 +345,10 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
     return hipErrorInvalidValue;
   }
   if (a.prec != 0) {  // the opt-in single-precision mode: its kernel or an error, never another family
+    if (a.cw_prof || a.prof) {
+      if (err) *err = "the iteration profile is not available in the f32 mode (a follow-up)";
+      return hipErrorNotSupported;
+    }
     if (a.prec != 1) {
       if (err) *err = "unknown BP precision";
       return hipErrorInvalidValue;
@@ -337,6 +360,23 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
     }
     if (family) *family = "bp_regular_f32_kernel";
     return e;
+  }
+  if (a.cw_prof || a.prof) {
+    // the iteration profile lives in the regular and the irregular LDS kernels
+    // only: their PROF instances or an error, never another family
+    const char *why = bp_profile_refusal(c, a.iter_count);
+    hipError_t e = why ? hipErrorNotSupported : launch_bp_regular(c, a, s);
+    if (!why && e != hipErrorNotSupported) {
+      if (family) *family = "bp_regular_kernel";
+      return e;
+    }
+    if (!why) e = launch_bp_irregular(c, a, s);
+    if (!why && e != hipErrorNotSupported) {
+      if (family) *family = "bp_irregular_kernel";
+      return e;
+    }
+    if (err) *err = why ? why : "the iteration profile is not available for this code or launch";
+    return hipErrorNotSupported;
   }
   const bool lds = bp_uses_lds(c);
   // kernel families, most specialised first: regular PEG2304-class (LDS),

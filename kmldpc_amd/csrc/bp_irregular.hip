@@ -42,6 +42,7 @@ namespace kml {
 namespace {
 
 constexpr int kRedBytes = 16;
+constexpr int kIrrProfMaxKw = 64;  // PROF: reference words staged in LDS (K <= 4096; launcher check)
 
 __device__ __forceinline__ double swap_pair(double x) {
   const int lo = __double2loint(x), hi = __double2hiint(x);
@@ -340,11 +341,15 @@ __device__ unsigned long long kml_irr_stamps[kIrrThreads / 64][8];
 // the caller re-initialises the slots and redoes the codeword with FAST =
 // false (decided at the CN closing barrier, before that iteration's
 // syndromes are written; see bp_regular.hip decode_reg).
-template <int T, bool SYN, bool FAST>
+// PROF (iteration profile, see bp_regular.hip decode_reg): between the VN
+// phase's closing barrier and the CN phase's closing wg_any the decision bytes
+// are iteration iter's; count_info_errors against the codeword's reference
+// words (pref, staged in LDS by the caller) goes into perr[iter].
+template <int T, bool SYN, bool FAST, bool PROF = false>
 __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, int cw, double2 *slots,
                                            const unsigned short *cslot, const double *p0s, unsigned char *cch, int odd,
                                            const int (&vcol)[3], const int (&crow)[3], int &iter_out, bool &conv_out,
-                                           bool sus0 = false) {
+                                           bool sus0 = false, const uint64_t *pref = nullptr, int *perr = nullptr) {
   // Each lane's plan packed into one word per round (slot base | degree << 14
   // | column or row << 18; ~0 = no item), built once per codeword: the
   // iteration loop makes no global loads.  The words are laundered at the top
@@ -407,6 +412,10 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
     IRR_STAMP(1);
     __syncthreads();
     IRR_STAMP(2);
+    if constexpr (PROF) {  // CntErr of iteration iter's decisions (lane 0 of each wave holds its words' count)
+      const int errs = count_info_errors<T>(cch, nullptr, c.info_off, c.K, c.Kw, pref, threadIdx.x);
+      if (errs) atomicAdd(&perr[iter], errs);
+    }
 
     // The early-stop parity of each row comes out of the CN pass (the row
     // halves' decisions ride in the v2c sign bits the chains load); the OR
@@ -475,11 +484,18 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
 
 // EXACT = false: the FAST kernel (defers non-FAST and suspect codewords);
 // EXACT = true: the exact path over the defer list (see bp_regular.hip).
-template <int T, bool SYN, bool EXACT>
+template <int T, bool SYN, bool EXACT, bool PROF = false>
 __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, unsigned int *queue, int fast_allowed) {
   const double plo = fast_prior_lo(c.dv_max);  // FAST prior domain (bp_common.hpp)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ __attribute__((aligned(16))) int pflags[16];  // wg_all of the FAST prior check (bp_common.hpp)
+  // PROF: the codeword's reference words and its error bits per iteration, and
+  // the workgroup's sums per budget {err_bit, err_blk, converged} (lane k alone
+  // touches wprof[k]; flushed at the exit)
+  __shared__ uint64_t pref[PROF ? kIrrProfMaxKw : 1];
+  __shared__ int perr[PROF ? kBpProfMaxIter : 1];
+  __shared__ unsigned long long wprof[PROF ? kBpProfMaxIter : 1][3];
+  static_assert(!PROF || !SYN, "the iteration profile has no syndrome output");
   const int tid = threadIdx.x;
   const int odd = tid & 1;
   double2 *slots = reinterpret_cast<double2 *>(smem);
@@ -498,6 +514,8 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
   }
 
   const int B = a.B_dev ? (int)*a.B_dev : a.B;  // the exact kernel: the FAST kernel's defer count
+  if constexpr (PROF)
+    if (tid < a.iter_count) wprof[tid][0] = wprof[tid][1] = wprof[tid][2] = 0;
   for (;;) {
     __syncthreads();
     if (tid == 0) {
@@ -511,6 +529,10 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
     const int cw = a.cw_idx ? a.cw_idx[entry] : entry;
     const double *p0 = a.p0 + (long long)cw * a.p0_stride;
     if (a.p0_sel) p0 += (long long)a.p0_sel[cw] * a.p0_sel_stride;
+    if constexpr (PROF) {  // (the last epilogue's reads are behind the barriers above; wg_all's is ahead)
+      if (tid < a.iter_count) perr[tid] = 0;
+      if (tid < c.Kw) pref[tid] = a.ref_bits[(long long)cw * c.Kw + tid];
+    }
 
     bool ok = true;
     for (int i = tid; i < c.cc_len; i += T) {
@@ -525,8 +547,8 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
     bool conv = false;
     if constexpr (!EXACT) {
       bool defer = !fast;
-      if (fast && decode_irr<T, SYN, true>(c, a, cw, slots, cslot, p0s, cch, odd, vcol, crow, iter, conv,
-                                           (fast_allowed & 2) != 0)) {
+      if (fast && decode_irr<T, SYN, true, PROF>(c, a, cw, slots, cslot, p0s, cch, odd, vcol, crow, iter, conv,
+                                                 (fast_allowed & 2) != 0, pref, perr)) {
         defer = true;  // an unproven quotient: the exact kernel redoes the codeword
         if (tid == 0 && a.counters) atomicAdd(&a.counters[CNT_REDONE], 1ull);
       }
@@ -535,7 +557,7 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
         continue;
       }
     } else {
-      decode_irr<T, SYN, false>(c, a, cw, slots, cslot, p0s, cch, odd, vcol, crow, iter, conv);
+      decode_irr<T, SYN, false, PROF>(c, a, cw, slots, cslot, p0s, cch, odd, vcol, crow, iter, conv, false, pref, perr);
     }
 
     if (a.iter_count > 0) {
@@ -563,6 +585,20 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
       }
     }
     __syncthreads();
+    if constexpr (PROF) {
+      // Budget k + 1 returns the decisions of iteration min(k, last), last = the
+      // last iteration whose VN phase ran, and converged when the parity check
+      // passed at an iteration <= k.  A deferred FAST decode never gets here:
+      // its counts stay in perr, which the next codeword zeroes.
+      if (tid < a.iter_count) {
+        const int last = conv ? iter : a.iter_count - 1;
+        const int e = perr[tid < last ? tid : last];
+        if (a.cw_prof) a.cw_prof[(long long)cw * a.cw_prof_stride + tid] = e;
+        wprof[tid][0] += (unsigned long long)e;
+        wprof[tid][1] += e > 0 ? 1ull : 0ull;
+        wprof[tid][2] += conv && iter <= tid ? 1ull : 0ull;
+      }
+    }
     if (tid == 0) {
       if (a.ret) a.ret[cw] = iter + (iter < a.max_iter);
       if (a.parity_cnt) a.parity_cnt[cw] = red[0];
@@ -583,17 +619,28 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
       }
     }
   }
+  if constexpr (PROF)
+    if (a.prof && tid < a.iter_count)  // the workgroup's sums (lane k's own)
+      for (int j = 0; j < 3; ++j)
+        if (wprof[tid][j]) atomicAdd(&a.prof[tid * 3 + j], wprof[tid][j]);
 }
 
 size_t irr_lds_bytes(const DevCode &c) {
   return (size_t)c.irr_slots * 16 + (size_t)c.E * 2 + (size_t)c.cc_len * 8 + kRedBytes + (size_t)c.N;
 }
 
-template <int T, bool SYN, bool EXACT>
+template <int T, bool SYN, bool EXACT, bool PROF = false>
 hipError_t launch_irr_one(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
-  auto kern = bp_irregular_kernel<T, SYN, EXACT>;
+  auto kern = bp_irregular_kernel<T, SYN, EXACT, PROF>;
   const size_t lds = irr_lds_bytes(c);
-  hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e;
+  if constexpr (PROF) {  // the profile's static LDS counts against the same limit
+    hipFuncAttributes fa;
+    e = hipFuncGetAttributes(&fa, (const void *)kern);
+    if (e != hipSuccess) return e;
+    if (lds + fa.sharedSizeBytes > 160 * 1024) return hipErrorNotSupported;
+  }
+  e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   int dev = 0, ncu = 0;
   hipGetDevice(&dev);
@@ -607,18 +654,18 @@ hipError_t launch_irr_one(const DevCode &c, const BpLaunch &a, hipStream_t s, in
 }
 
 // FAST kernel, then the exact kernel over its defer list (bp_regular.hip launch_reg_t)
-template <int T, bool SYN>
+template <int T, bool SYN, bool PROF = false>
 hipError_t launch_irr_t(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
-  if (!(fast_allowed & 1)) return launch_irr_one<T, SYN, true>(c, a, s, 0);
+  if (!(fast_allowed & 1)) return launch_irr_one<T, SYN, true, PROF>(c, a, s, 0);
   if (!a.defer_idx || !a.defer_cnt) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(a.defer_cnt, 0, sizeof(unsigned), s);
   if (e != hipSuccess) return e;
-  e = launch_irr_one<T, SYN, false>(c, a, s, fast_allowed);
+  e = launch_irr_one<T, SYN, false, PROF>(c, a, s, fast_allowed);
   if (e != hipSuccess) return e;
   BpLaunch b = a;
   b.cw_idx = a.defer_idx;
   b.B_dev = a.defer_cnt;
-  return launch_irr_one<T, SYN, true>(c, b, s, 0);
+  return launch_irr_one<T, SYN, true, PROF>(c, b, s, 0);
 }
 
 }  // namespace
@@ -628,6 +675,11 @@ hipError_t launch_bp_irregular(const DevCode &c, const BpLaunch &a, hipStream_t 
   if (irr_lds_bytes(c) > 160 * 1024 || c.irr_slots > 16383) return hipErrorNotSupported;
   if (!c.irr_ok || !c.irr_vn) return hipErrorNotSupported;
   const int fast = bp_fast_mode(c);
+  if (a.cw_prof || a.prof) {  // the iteration profile: its own instances (SYN = false), or an error
+    if (a.syn || !a.ref_bits || a.iter_count < 1) return hipErrorInvalidValue;
+    if (a.iter_count > kBpProfMaxIter || c.Kw > kIrrProfMaxKw) return hipErrorNotSupported;
+    return launch_irr_t<T, false, true>(c, a, s, fast);
+  }
   return a.syn ? launch_irr_t<T, true>(c, a, s, fast) : launch_irr_t<T, false>(c, a, s, fast);
 }
 

@@ -156,12 +156,23 @@ __device__ __forceinline__ double with_sign(double x, int bit) {
 // before that iteration's syndromes are written, so everything a suspect
 // decode wrote (slots, decisions, syndromes of earlier iterations) is what the
 // exact decode rewrites identically or overwrites.
-template <int T, int RV, int RC, int DV, int DC, bool SYN, bool FAST>
+//
+// PROF (iteration profile, kernels.hpp BpLaunch::cw_prof / prof): after the VN
+// phase's closing barrier of iteration iter the decision bytes are that
+// iteration's hard decisions (what a decode with budget iter + 1 returns unless
+// it converged earlier), and nothing writes them before the next VN phase,
+// which starts after the CN phase's closing wg_any.  Between the two barriers
+// every wave counts its info-bit words against refw exactly as the epilogue's
+// CntErr does and adds the sum into perr[iter] (LDS, zeroed by the caller
+// before the loop's first barrier): no barrier of its own.
+template <int T, int RV, int RC, int DV, int DC, bool SYN, bool FAST, bool PROF = false>
 __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, int cw, unsigned char *smem,
                                            unsigned hd, const unsigned (&vaddr)[RV][DV], const double (&pv)[RV],
                                            const int (&crow)[RC], const unsigned (&rb)[RC], const unsigned (&rb2)[RC],
                                            const unsigned (&wb)[RC], int odd, int &iter_out, bool &conv_out,
-                                           bool sus0 = false) {
+                                           bool sus0 = false, const unsigned char *cch = nullptr,
+                                           const unsigned short *ipos = nullptr, const uint64_t *refw = nullptr,
+                                           int *perr = nullptr) {
   static_assert(DC % 2 == 0, "the lane-pair split assumes an even row degree");
   constexpr int H = DC / 2;
   __shared__ __attribute__((aligned(16))) int wflags[16];  // wg_any (bp_common.hpp)
@@ -262,6 +273,21 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     REG_WSTAMP(0);
     __syncthreads();
     REG_WSTAMP(1);
+    if constexpr (PROF) {  // CntErr of iteration iter's decisions (the epilogue's, word for word)
+      const int lane = threadIdx.x & 63;
+      int errs = 0;
+      for (int w0 = threadIdx.x >> 6; w0 < c.Kw; w0 += 2 * (T / 64)) {
+        const int w1 = w0 + T / 64;
+        const uint64_t r0 = refw[w0];
+        const uint64_t r1 = w1 < c.Kw ? refw[w1] : 0ull;
+        const int i0 = w0 * 64 + lane, i1 = w1 * 64 + lane;
+        const int b0 = i0 < c.K ? cch[ipos[i0]] : 0;
+        const int b1 = i1 < c.K && w1 < c.Kw ? cch[ipos[i1]] : 0;
+        const uint64_t m0 = __ballot(b0), m1 = __ballot(b1);
+        errs += __popcll(m0 ^ r0) + (w1 < c.Kw ? __popcll(m1 ^ r1) : 0);
+      }
+      if (lane == 0 && errs) atomicAdd(&perr[iter], errs);
+    }
 
     // The early-stop parity check rides on the CN phase: in steps 0..H-1 the
     // even lane loads the row's edges [0, H) and the odd lane [H, DC), whose
@@ -406,7 +432,7 @@ constexpr size_t reg_lds_bytes(int E, int N, int K, int DMB) { return ipos_offse
 // EXACT = true: decodes its entries (the defer list) on the exact path (div_rn).
 // Two kernels rather than one with both paths: the exact path's registers
 // would otherwise be allocated (and spilled) in the FAST kernel too.
-template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT>
+template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT, bool PROF = false>
 __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, unsigned int *queue, int fast_allowed) {
   const double plo = fast_prior_lo(c.dv_max);  // FAST prior domain (bp_common.hpp)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -416,6 +442,11 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
   __shared__ uint64_t detab[DMB > 0 ? 256 : 1];
   __shared__ uint64_t refw[kRegMaxKw];                    // this codeword's reference bits
   __shared__ unsigned long long wcnt[CNT_CONVERGED + 1];  // the workgroup's counters
+  // PROF: the codeword's error bits per iteration, and the workgroup's sums per
+  // budget {err_bit, err_blk, converged} (lane k alone touches wprof[k])
+  __shared__ int perr[PROF ? kBpProfMaxIter : 1];
+  __shared__ unsigned long long wprof[PROF ? kBpProfMaxIter : 1][3];
+  static_assert(!PROF || !SYN, "the iteration profile has no syndrome output");
   double *p0s = reinterpret_cast<double *>(smem + p0s_offset(c.E, c.N));
   if constexpr (DMB > 0) {
     for (int k = threadIdx.x; k < (2 << DMB); k += T) dcons[k] = a.sym_cons[k];
@@ -464,6 +495,8 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
   const int B = a.B_dev ? (int)*a.B_dev : a.B;  // the exact kernel: the FAST kernel's defer count
   const bool ref_pre = a.ref_bits && a.iter_count > 0;  // (c.Kw <= kRegMaxKw: host check)
   if (a.counters && tid <= CNT_CONVERGED) wcnt[tid] = 0;  // ordered by the loop's first barrier
+  if constexpr (PROF)
+    if (tid < a.iter_count) wprof[tid][0] = wprof[tid][1] = wprof[tid][2] = 0;
   if (tid == 0) {  // the first entry; then each codeword's epilogue takes the next
     red[3] = (int)atomicAdd(queue, 1u);
     red[0] = 0;
@@ -475,6 +508,8 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
     REG_STAMP(0);
     if (entry >= B) break;
     const int cw = a.cw_idx ? a.cw_idx[entry] : entry;
+    if constexpr (PROF)  // (the last epilogue's reads are behind the barrier above; the first VN barrier is ahead)
+      if (tid < a.iter_count) perr[tid] = 0;
     if (ref_pre && tid < 2 * c.Kw)  // one dword per lane (the first waves), in flight through the prologue
       __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned *>(a.ref_bits + (long long)cw * c.Kw) + tid,
                                        (__attribute__((address_space(3))) void *)(reinterpret_cast<unsigned *>(refw) +
@@ -522,8 +557,9 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
     bool conv = false;
     if constexpr (!EXACT) {
       bool defer = !fast;
-      if (fast && decode_reg<T, RV, RC, DV, DC, SYN, true>(c, a, cw, smem, cch_a + tid, vaddr, pv, crow, rb, rb2, wb,
-                                                           odd, iter, conv, (fast_allowed & 2) != 0)) {
+      if (fast && decode_reg<T, RV, RC, DV, DC, SYN, true, PROF>(c, a, cw, smem, cch_a + tid, vaddr, pv, crow, rb, rb2,
+                                                                 wb, odd, iter, conv, (fast_allowed & 2) != 0, cch, ipos,
+                                                                 refw, perr)) {
         defer = true;  // an unproven quotient: the exact kernel redoes the codeword
         if (tid == 0 && a.counters) atomicAdd(&a.counters[CNT_REDONE], 1ull);
       }
@@ -535,8 +571,8 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
         continue;
       }
     } else {
-      decode_reg<T, RV, RC, DV, DC, SYN, false>(c, a, cw, smem, cch_a + tid, vaddr, pv, crow, rb, rb2, wb, odd, iter,
-                                               conv);
+      decode_reg<T, RV, RC, DV, DC, SYN, false, PROF>(c, a, cw, smem, cch_a + tid, vaddr, pv, crow, rb, rb2, wb, odd,
+                                                     iter, conv, false, cch, ipos, refw, perr);
     }
 
     REG_STAMP(3);
@@ -590,6 +626,20 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
     }
     __syncthreads();
     REG_STAMP(4);
+    if constexpr (PROF) {
+      // Budget k + 1 returns the decisions of iteration min(k, last), last = the
+      // last iteration whose VN phase ran; it converged when the parity check
+      // passed at an iteration <= k.  Only a decode that finished gets here: a
+      // deferred FAST decode left its counts in perr, zeroed again above.
+      if (tid < a.iter_count) {
+        const int last = conv ? iter : a.iter_count - 1;
+        const int e = perr[tid < last ? tid : last];
+        if (a.cw_prof) a.cw_prof[(long long)cw * a.cw_prof_stride + tid] = e;
+        wprof[tid][0] += (unsigned long long)e;
+        wprof[tid][1] += e > 0 ? 1ull : 0ull;
+        wprof[tid][2] += conv && iter <= tid ? 1ull : 0ull;
+      }
+    }
     if (tid == 0) {
       if (a.ret) a.ret[cw] = iter + (iter < a.max_iter);
       if (a.parity_cnt) a.parity_cnt[cw] = red[0];
@@ -618,17 +668,28 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
   if (a.counters && tid == 0)  // the workgroup's sums (only thread 0 wrote them)
     for (int i = 0; i <= CNT_CONVERGED; ++i)
       if (wcnt[i]) atomicAdd(&a.counters[i], wcnt[i]);
+  if constexpr (PROF)
+    if (a.prof && tid < a.iter_count)  // (lane k's own sums)
+      for (int j = 0; j < 3; ++j)
+        if (wprof[tid][j]) atomicAdd(&a.prof[tid * 3 + j], wprof[tid][j]);
 #if KML_STAMPS
   if (tid == 0)
     for (int i = 0; i < 8; ++i) atomicAdd(&kml_reg_stamps[i], rs_acc[i]);
 #endif
 }
 
-template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT>
+template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT, bool PROF = false>
 hipError_t launch_reg_one(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
-  auto kern = bp_regular_kernel<T, RV, RC, DV, DC, SYN, DMB, EXACT>;
+  auto kern = bp_regular_kernel<T, RV, RC, DV, DC, SYN, DMB, EXACT, PROF>;
   const size_t lds = reg_lds_bytes(c.E, c.N, c.K, DMB);
-  hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e;
+  if constexpr (PROF) {  // the profile's static LDS counts against the same limit
+    hipFuncAttributes fa;
+    e = hipFuncGetAttributes(&fa, (const void *)kern);
+    if (e != hipSuccess) return e;
+    if (lds + fa.sharedSizeBytes > 160 * 1024) return hipErrorNotSupported;
+  }
+  e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   int dev = 0, ncu = 0;
   hipGetDevice(&dev);
@@ -644,20 +705,20 @@ hipError_t launch_reg_one(const DevCode &c, const BpLaunch &a, hipStream_t s, in
 // The FAST kernel over the batch, then the exact kernel over the codewords it
 // deferred (usually none: its workgroups read a zero count and leave); with
 // FAST division off, the exact kernel over the batch.
-template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB>
+template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool PROF = false>
 hipError_t launch_reg_t(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
   const size_t lds = reg_lds_bytes(c.E, c.N, c.K, DMB);
   if (lds > 160 * 1024 || c.K > 65536 || c.N > 65536 || c.Kw > kRegMaxKw) return hipErrorNotSupported;
-  if (!(fast_allowed & 1)) return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true>(c, a, s, 0);
+  if (!(fast_allowed & 1)) return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true, PROF>(c, a, s, 0);
   if (!a.defer_idx || !a.defer_cnt) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(a.defer_cnt, 0, sizeof(unsigned), s);
   if (e != hipSuccess) return e;
-  e = launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, false>(c, a, s, fast_allowed);
+  e = launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, false, PROF>(c, a, s, fast_allowed);
   if (e != hipSuccess) return e;
   BpLaunch b = a;
   b.cw_idx = a.defer_idx;
   b.B_dev = a.defer_cnt;
-  return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true>(c, b, s, 0);
+  return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true, PROF>(c, b, s, 0);
 }
 
 }  // namespace
@@ -673,6 +734,15 @@ hipError_t launch_bp_regular(const DevCode &c, const BpLaunch &a, hipStream_t s)
   if (!c.reg_c2v || bp_regular_threads(c.N, c.M, c.E, c.dv_max, c.dc_max, c.regular) != 768)
     return hipErrorNotSupported;
   const int fast = bp_fast_mode(c);
+  if (a.cw_prof || a.prof) {  // the iteration profile: its own instances (SYN = false), or an error
+    if (a.syn || !a.ref_bits || a.iter_count < 1) return hipErrorInvalidValue;
+    if (a.iter_count > kBpProfMaxIter) return hipErrorNotSupported;
+    if (a.sym_y) {
+      if (!bp_regular_fuses_demap(c, a.sym_bits) || a.cw_idx || a.p0_sel) return hipErrorNotSupported;
+      return launch_reg_t<768, 3, 3, 3, 6, false, 2, true>(c, a, s, fast);
+    }
+    return launch_reg_t<768, 3, 3, 3, 6, false, 0, true>(c, a, s, fast);
+  }
   if (a.sym_y) {
     if (!bp_regular_fuses_demap(c, a.sym_bits) || a.cw_idx || a.p0_sel) return hipErrorNotSupported;
     return a.syn ? launch_reg_t<768, 3, 3, 3, 6, true, 2>(c, a, s, fast)

@@ -97,6 +97,7 @@ struct kml_ctx {
   DBuf w_ddefer;  // demap / candidate-metric launches: the same for symbols or codewords
   // workspaces
   DBuf w_y, w_h, w_h4, w_hhat, w_p0, w_uu, w_uh, w_uh4, w_ret, w_cch, w_syn, w_sel, w_met, w_pc, w_cnt, w_km, w_cwerr;
+  DBuf w_prof, w_cwprof;  // kml_sim_decode_profile: prof[P][3], cw_prof[B][P]
   // soft syndrome metric: candidate / final syndromes, iteration counts, sums, decode lists
   DBuf s_synm, s_synf, s_itm, s_itf, s_Lm, s_Lf, s_list, s_sel;
   // Sum of log(syndrom_soft) of the most recent decode that ran a CN phase on
@@ -552,6 +553,9 @@ struct RecvIO {
   double2 *hhat = nullptr;          // [B] k-means h_hat
   const uint64_t *ref_bits = nullptr;  // packed source bits for CntErr
   int32_t *cw_err = nullptr;           // [B] error bits per codeword
+  // iteration profile of the final decode (kml_sim_decode_profile; kernels.hpp BpLaunch::cw_prof / prof)
+  int32_t *cw_prof = nullptr;          // [B][max_iter]
+  unsigned long long *prof = nullptr;  // [max_iter][3]
   // GetHistogramData instead of Decoder (simulator.cc:154-162): candidate
   // metrics only, no final decode; CntErr then sees the uu_hat left by the last
   // candidate's metric decode (5G metric), or all zeros for the hard PEG metric
@@ -583,6 +587,9 @@ int receive(kml_ctx *c, const RecvIO &io, double snr, int B, int &bp_slot) {
   a.ret = io.ret;
   a.ref_bits = io.ref_bits;
   a.cw_err = io.cw_err;
+  a.cw_prof = io.cw_prof;  // the final decode only: the candidate-metric launches below are their own BpLaunch
+  a.cw_prof_stride = c->rc.max_iter;
+  a.prof = io.prof;
   if (io.true_h && !io.histogram && kml::bp_regular_fuses_demap(c->dc, c->modem.bits)) {
     // known channel on the regular kernel: the demap runs in its prologue
     a.sym_y = io.y;
@@ -971,7 +978,7 @@ void kml_destroy(kml_ctx *c) {
     c->w_ddefer.release();
     for (DBuf *b : {&c->d_graph, &c->d_cons, &c->d_arena, &c->d_queue, &c->d_gslots, &c->d_gsync, &c->d_gcch, &c->w_y, &c->w_h, &c->w_h4,
                     &c->w_hhat, &c->w_p0, &c->w_uu, &c->w_uh, &c->w_uh4, &c->w_cwerr, &c->w_ret, &c->w_cch, &c->w_syn, &c->w_sel, &c->w_met,
-                    &c->w_pc, &c->w_cnt, &c->w_km, &c->s_synm, &c->s_synf, &c->s_itm, &c->s_itf, &c->s_Lm, &c->s_Lf, &c->s_list, &c->s_sel, &c->s_uu, &c->s_cc, &c->s_y, &c->s_h, &c->w_hc})
+                    &c->w_pc, &c->w_cnt, &c->w_km, &c->s_synm, &c->s_synf, &c->s_itm, &c->s_itf, &c->s_Lm, &c->s_Lf, &c->s_list, &c->s_sel, &c->s_uu, &c->s_cc, &c->s_y, &c->s_h, &c->w_hc, &c->w_prof, &c->w_cwprof})
       b->release();
     hipStreamDestroy(c->stream);
     if (c->cstream) hipStreamDestroy(c->cstream);
@@ -1550,8 +1557,11 @@ int kml_sim_generate(kml_ctx *c, double snr, uint64_t seed, uint64_t first_cw, i
 }
 
 namespace {
-int sim_receive(kml_ctx *c, double snr, int blind, bool histogram, int &slot) {
+int sim_receive(kml_ctx *c, double snr, int blind, bool histogram, int &slot, int32_t *cw_prof = nullptr,
+                unsigned long long *prof = nullptr) {
   RecvIO io;
+  io.cw_prof = cw_prof;
+  io.prof = prof;
   io.y = c->s_y.as<double2>();
   io.true_h = blind ? nullptr : c->s_h.as<double2>();
   io.ref_bits = c->s_uu.as<uint64_t>();
@@ -1610,6 +1620,48 @@ int kml_sim_decode_ex(kml_ctx *c, double snr, int blind, int histogram, int32_t 
     else
       memset(metrics, 0, sizeof(double) * 4 * B);
   }
+  TRY(sync(c));
+  if (counters)
+    for (int i = 0; i < kml::CNT_N; i++) counters[i] = h[i];
+  return KML_OK;
+}
+
+int kml_sim_decode_profile(kml_ctx *c, double snr, int blind, uint64_t *prof, int32_t *cw_prof, uint64_t *counters) {
+  call_begin(c);
+  if (!c) return KML_E_ARG;
+  // every refusal is decided here, before anything is launched
+  if (c->device < 0 || !c->stream)
+    return fail(c, KML_E_UNSUP, "kml_sim_decode_profile: host-only context (device < 0): no GPU operations");
+  const int P = c->rc.max_iter;
+  if (P < 1) return fail(c, KML_E_ARG, "kml_sim_decode_profile: max_iter must be >= 1");
+  if (c->precision != KML_PREC_F64)
+    return fail(c, KML_E_UNSUP, "kml_sim_decode_profile: the iteration profile is not available in the f32 mode");
+  if (c->rc.metric_soft)
+    return fail(c, KML_E_UNSUP,
+                "kml_sim_decode_profile: the iteration profile is not available with the soft-syndrome metric "
+                "(metric_type = 1)");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  if (const char *why = kml::bp_profile_refusal(c->dc, P))
+    return fail(c, KML_E_UNSUP, std::string("kml_sim_decode_profile: ") + why);
+  const int B = c->sim_B;
+  if (prof) memset(prof, 0, sizeof(uint64_t) * 3 * (size_t)P);
+  if (B == 0) {
+    if (counters) memset(counters, 0, sizeof(uint64_t) * kml::CNT_N);
+    return KML_OK;
+  }
+  HIPCHK(c, c->w_prof.ensure(sizeof(unsigned long long) * 3 * (size_t)P), "hipMalloc(prof)");
+  HIPCHK(c, c->w_cwprof.ensure(sizeof(int32_t) * (size_t)B * P), "hipMalloc(cw_prof)");
+  HIPCHK(c, hipMemsetAsync(c->w_prof.p, 0, sizeof(unsigned long long) * 3 * (size_t)P, c->stream), "memset");
+  int slot = 0;
+  TRY(sim_receive(c, snr, blind, false, slot, c->w_cwprof.as<int32_t>(), c->w_prof.as<unsigned long long>()));
+  unsigned long long h[kml::CNT_N];
+  HIPCHK(c, hipMemcpyAsync(h, slot_ptr(c, slot), sizeof(h), hipMemcpyDeviceToHost, c->stream), "D2H");
+  if (prof)
+    HIPCHK(c, hipMemcpyAsync(prof, c->w_prof.p, sizeof(uint64_t) * 3 * (size_t)P, hipMemcpyDeviceToHost, c->stream),
+           "D2H");
+  if (cw_prof)
+    HIPCHK(c, hipMemcpyAsync(cw_prof, c->w_cwprof.p, sizeof(int32_t) * (size_t)B * P, hipMemcpyDeviceToHost, c->stream),
+           "D2H");
   TRY(sync(c));
   if (counters)
     for (int i = 0; i < kml::CNT_N; i++) counters[i] = h[i];

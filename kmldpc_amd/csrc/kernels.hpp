@@ -102,13 +102,30 @@ struct BpLaunch {
   // (bp_regular_f32.hip, PEG2304-class codes only; launch_bp fails for any
   // other code, there is no fallback in either direction)
   int prec = 0;
+  // Iteration profile (bp_regular.hip / bp_irregular.hip only, SYN = false,
+  // ref_bits set, 1 <= iter_count <= kBpProfMaxIter): when either is set the
+  // launch runs the PROF kernels, which count the info-bit errors of every
+  // iteration's decisions and report, for every budget k = 1..iter_count, what
+  // a decode with iter_count = k would have counted on the same codeword:
+  //   cw_prof[cw * cw_prof_stride + k-1] = error bits at budget k
+  //   prof[(k-1) * 3 + {0, 1, 2}]       += {error bits, codewords in error, converged} at budget k
+  // Any other kernel family answers hipErrorNotSupported (launch_bp: no fallback).
+  int32_t *cw_prof = nullptr;
+  long long cw_prof_stride = 0;
+  unsigned long long *prof = nullptr;
 };
+
+constexpr int kBpProfMaxIter = 64;  // budgets of a profile launch (static LDS: perr + wprof, 1792 B)
 
 // FAST-path mode of a BP launch: bit 0 = FAST division allowed (column degree
 // <= kFastMaxColumnDegree, and not KML_NO_FAST=1: every codeword on the
 // exact path); bit 1 = KML_FORCE_REDO=1 (tests: every FAST decode is treated
 // as suspect and redone on the exact path, exercising the redo machinery).
 int bp_fast_mode(const DevCode &c);
+// Why a profile launch (BpLaunch::cw_prof / prof) with this budget cannot run
+// for this code, or NULL when it can: the host-side check callers make before
+// they launch anything (launch_bp repeats it).
+const char *bp_profile_refusal(const DevCode &c, int iter_count);
 hipError_t launch_bp_regular(const DevCode &c, const BpLaunch &a, hipStream_t s);
 // Can the regular kernel compute P0 itself (BpLaunch::sym_y) for this code and modem?
 bool bp_regular_fuses_demap(const DevCode &c, int bits);
