@@ -326,6 +326,11 @@ int upload_code(kml_ctx *c) {
   c->coop_groups = kml::bp_coop_groups(d);
   if (c->coop_groups > 0) {
     HIPCHK(c, c->d_gsync.ensure(kml::bp_coop_sync_bytes(c->coop_groups)), "hipMalloc(gsync)");
+    // "no abort" from the start: run_bp marks a launch pending before it knows
+    // its family, and one that lands on the generic bp_kernel (KML_BP_KERNEL=
+    // generic, or the cooperative launcher declining) never writes the abort
+    // word that sync() then reads
+    HIPCHK(c, hipMemset(c->d_gsync.p, 0, kml::bp_coop_sync_bytes(c->coop_groups)), "memset(gsync)");
     HIPCHK(c, c->d_gcch.ensure((size_t)c->coop_groups * L.N), "hipMalloc(gcch)");
   }
   return KML_OK;

@@ -16,6 +16,9 @@ What it writes (all small):
                                   files (config/*.txt), gzip'd, so the tests and
                                   the GPU box have the on-disk inputs without
                                   /root/reference.  Data, not source.
+                                  (the synthetic H files data/syn_*.txt.gz are our
+                                  own, written by tests/golden/make_codes.py; their
+                                  cases, SYN_CASES, read them from there)
   tests/golden/<case>.npz         per case, seed 17 (CLCRandNum::SetSeed(-1)):
       * stream  : per-codeword chosen candidate, BP return value, error bits and
                   CRC32s of y / P0 / uu_hat / cc_hat / syndrom_soft
@@ -127,13 +130,50 @@ for _snr in SWEEP_SNRS:
         BENCH_CASES[f"peg8064_64qam_blind_s{int(round(_snr * 100))}_1024"] = (
             "PEG8064regular0.5.txt", "6bits_64QAM_Gray.txt", False, False, 20, _snr, 1024, True)
 
+# The synthetic codes (tests/golden/make_codes.py, data/syn_*.txt.gz): the
+# matrix comes from the repo's own data directory.  Each stream must hold both
+# kinds of codeword: at least a quarter that stop early (ret < max_iter) and a
+# quarter that run to max_iter, and the stored vectors one of each (SYN_CASES
+# are checked in make_frames_cases), so the SNRs sit in the waterfall.
+SYN_CASES = {
+    # bp_irregular_kernel, non-5G, K = 600; S = 600 (QPSK) and 300 (16QAM)
+    "syn_irr1200_qpsk_known": ("syn_irr1200.txt", "2bits_QPSK.txt", False, True, 30, 2.0, 60, True),
+    "syn_irr1200_16qam_blind": ("syn_irr1200.txt", "4bit_16QAM_Gray.txt", False, False, 20, 10.0, 60, True),
+    "syn_irr1200_qpsk_known_inactive": ("syn_irr1200.txt", "2bits_QPSK.txt", False, True, 30, 2.0, 40, False),
+    # bp_kernel in LDS: <3,6>, <12,12> (rank 119, K = 121), <32,32> (K = 60)
+    "syn_reg36_192_qpsk_blind": ("syn_reg36_192.txt", "2bits_QPSK.txt", False, False, 20, 3.0, 100, True),
+    "syn_reg48_240_16qam_known": ("syn_reg48_240.txt", "4bit_16QAM_Gray.txt", False, True, 20, 8.5, 100, True),
+    "syn_high120_qpsk_known": ("syn_high120.txt", "2bits_QPSK.txt", False, True, 20, 2.0, 100, True),
+    # bp_kernel with global slots; bp_part_kernel at NG = 1040
+    "syn_reg36_4080_16qam_blind": ("syn_reg36_4080.txt", "4bit_16QAM_Gray.txt", False, False, 20, 6.5, 24, True),
+    "syn_reg36_4160_qpsk_known": ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, True, 20, 2.2, 24, True),
+}
+CASES.update(SYN_CASES)
+NVEC_CASE.update({"syn_reg36_4080_16qam_blind": 4, "syn_reg36_4160_qpsk_known": 4})
+MAX_NPZ = 926645  # no new fixture is larger than the largest committed before the synthetic codes
+
 COUNTER_CASES = {
     "peg2304_qpsk_known_2000": ("PEG2304regular0.5.txt", "2bits_QPSK.txt", False, True, 20, 2.0, 2000, True),
     "peg2304_qpsk_blind_2000": ("PEG2304regular0.5.txt", "2bits_QPSK.txt", False, False, 20, 2.0, 2000, True),
 }
 
 
+def matrix_path(tmp, matrix):
+    """The reference's config/ file, or (the synthetic codes) the repo's own
+    tests/golden/data/<matrix>.gz unpacked into tmp."""
+    ref = os.path.join(REF_CFG, matrix)
+    if os.path.exists(ref):
+        return ref
+    out = os.path.join(tmp, matrix)
+    if not os.path.exists(out):
+        with gzip.open(os.path.join(HERE, "data", matrix + ".gz"), "rb") as g, open(out + ".part", "wb") as f:
+            f.write(g.read())
+        os.replace(out + ".part", out)
+    return out
+
+
 def write_toml(path, data_dir, matrix, modem, is5g, known, max_iter, active, metric_iter=5, soft=False):
+    """matrix: a file name in data_dir, or an absolute path (matrix_path)."""
     b = lambda v: "true" if v else "false"
     with open(path, "w") as f:
         f.write(f"""[range]
@@ -344,6 +384,15 @@ def check_direct(name, recs):
     assert not bad, f"{name}: KmCodec uu_hat != direct decode on codewords {bad[:10]}"
 
 
+def check_both_kinds(name, recs, max_iter, nv):
+    """Early-stopping codewords and codewords that run to max_iter: at least a
+    quarter of the stream each, and one of each among the nv stored vectors."""
+    full = np.array([d["ret"] == max_iter for d in recs])
+    assert 4 * full.sum() >= len(recs) and 4 * (~full).sum() >= len(recs), \
+        f"{name}: {int(full.sum())} of {len(recs)} codewords run to max_iter"
+    assert full[:nv].any() and not full[:nv].all(), f"{name}: the stored vectors hold one kind only: {full[:nv]}"
+
+
 def frames_arrays(hdr, cons, recs, mat, mod, active, nv):
     arrs = {
         "hdr_json": np.frombuffer(json.dumps(dict(hdr, matrix=mat, modem=mod, active=active)).encode(), dtype=np.uint8),
@@ -372,15 +421,18 @@ def make_frames_cases(tmp, names, check_only=False):
     def one(name):
         mat, mod, is5g, known, it, snr, n, active = CASES[name]
         cfg = os.path.join(tmp, name + ".toml")
-        write_toml(cfg, REF_CFG, mat, mod, is5g, known, it, active)
+        write_toml(cfg, REF_CFG, matrix_path(tmp, mat), mod, is5g, known, it, active)
         out = os.path.join(tmp, name + ".bin")
         subprocess.run([HARNESS, cfg, repr(snr), str(n), out], check=True)
         hdr, cons, recs = parse_frames(open(out, "rb").read())
         check_direct(name, recs)
+        if name in SYN_CASES:
+            check_both_kinds(name, recs, it, min(NVEC_CASE.get(name, NVEC), len(recs)))
         if check_only:
             return f"{name}: n={n} KmCodec::Decoder == direct BinaryLDPCCodec::Decoder on every codeword"
         arrs = frames_arrays(hdr, cons, recs, mat, mod, active, min(NVEC_CASE.get(name, NVEC), len(recs)))
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrs)
+        assert name not in SYN_CASES or os.path.getsize(os.path.join(HERE, name + ".npz")) <= MAX_NPZ, name
         return f"{name}: n={n} FER={np.mean(arrs['s_errs'] > 0):.4f} mean_ret={arrs['s_ret'].mean():.2f}"
 
     with ThreadPoolExecutor(4) as ex:

@@ -75,7 +75,7 @@ static void check_code(const std::string &path, bool is5g, const Modem &modem, i
       RegularLayout rl;
       plan_regular_layout(L, 1024, rl);
     }
-    if (is5g) {
+    if (is5g || L.dv_max != 3) {  // (any non-(3,6) code: whatever it returns, it returns cleanly)
       IrregularPlan ip;
       plan_irregular(L, kIrrThreads, kIrrVnPairMax, kIrrCnPairMax, ip);
     }
@@ -175,9 +175,12 @@ int main(int argc, char **argv) {
   qpsk.load(data + "/2bits_QPSK.txt", err);
   qam16.load(data + "/4bit_16QAM_Gray.txt", err);
   qam64.load(data + "/6bits_64QAM_Gray.txt", err);
-  const char *codes[] = {"PEG2304regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt", "PEG8064regular0.5.txt"};
-  const Modem *cm[] = {&qpsk, &qam16, &qam64};
-  for (int k = 0; k < 3; k++) {
+  // the reference's three H files, then the synthetic ones (tests/golden/make_codes.py)
+  const char *codes[] = {"PEG2304regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt", "PEG8064regular0.5.txt",
+                         "syn_irr1200.txt",       "syn_reg36_192.txt",        "syn_reg48_240.txt",
+                         "syn_high120.txt",       "syn_reg36_4080.txt",       "syn_reg36_4160.txt"};
+  const Modem *cm[] = {&qpsk, &qam16, &qam64, &qam64, &qpsk, &qam16, &qam64, &qam64, &qpsk};
+  for (int k = 0; k < 9; k++) {
     spit(scratch + "/" + codes[k], slurp(data + "/" + codes[k]));
     check_code(scratch + "/" + codes[k], k == 1, *cm[k], -1 - k);
   }

@@ -1,9 +1,14 @@
 // Host checks of the kernels' placement plans (layout.cpp) on the reference's
 // H files: every plan is a valid assignment of columns / rows / slots to lanes
 // with the properties the kernels rely on.  Prints "plan_errors=0" on success.
-//   plan_check <PEG2304 H> <BG2 H> <PEG8064 H>
+//   plan_check <PEG2304 H> <BG2 H> <PEG8064 H> [--irregular F | --partition F | --none F]...
+// The extra (non-5G) H files are checked in the named role: the irregular
+// plan (with a census line of what its waves hold), the partition plan, or
+// neither plan being made (the code decodes on the generic bp_kernel).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <set>
 #include <string>
 #include <vector>
@@ -66,9 +71,48 @@ static void check_regular(const LdpcCode &L) {
   printf("regular: bank-conflict cost %lld -> %lld\n", P.cost_initial, P.cost_final);
 }
 
+static std::string set_str(const std::set<int> &s) {
+  std::string o = "{";
+  for (int d : s) o += (o.size() > 1 ? "," : "") + std::to_string(d);
+  return o + "}";
+}
+
+// What the waves of an irregular plan hold, per phase: the degrees that occur
+// paired (rounds 0-1: a lane's two columns, a lane pair's two rows) and single
+// (round 2), and the number of waves that mix degrees, that are idle (a pair
+// wave without a pair, a single wave without a node) and of partly filled pair
+// waves.  One line per phase:
+//   census <name> <vn|cn>: paired {..} single {..} mixed A idle B partial_pair C
+static void irregular_census(const LdpcCode &L, const IrregularPlan &P, int T, const char *name) {
+  for (int phase = 0; phase < 2; phase++) {
+    const int per_wave = phase ? 32 : 64, n = phase ? T / 2 : T;  // positions per wave / per round
+    const std::vector<int32_t> &a = phase ? P.cn : P.vn;
+    auto deg = [&](int x) { return phase ? row_deg(L, x) : col_deg(L, x); };
+    std::set<int> paired, single;
+    int mixed = 0, idle = 0, partial = 0;
+    for (int w = 0; w < n / per_wave; w++) {
+      std::set<int> dp, ds;
+      int np = 0;
+      for (int i = w * per_wave; i < (w + 1) * per_wave; i++) {
+        if (a[i] >= 0) dp.insert(deg(a[i])), np++;
+        if (a[n + i] >= 0) dp.insert(deg(a[n + i]));
+        if (a[2 * n + i] >= 0) ds.insert(deg(a[2 * n + i]));
+      }
+      paired.insert(dp.begin(), dp.end());
+      single.insert(ds.begin(), ds.end());
+      mixed += (dp.size() > 1) + (ds.size() > 1);
+      idle += dp.empty() + ds.empty();
+      partial += np > 0 && np < per_wave;
+    }
+    printf("census %s %s: paired %s single %s mixed %d idle %d partial_pair %d\n", name, phase ? "cn" : "vn",
+           set_str(paired).c_str(), set_str(single).c_str(), mixed, idle, partial);
+  }
+}
+
 // bp_irregular.hip: three rounds, pairs of equal degree (up to the limits) in
 // rounds 0-1, every column / row exactly once, one degree per paired wave.
-static void check_irregular(const LdpcCode &L) {
+// census: the name to print the census of the plan under.
+static void check_irregular(const LdpcCode &L, const char *census = nullptr) {
   const int T = kIrrThreads;
   IrregularPlan P;
   CHECK(plan_irregular(L, T, kIrrVnPairMax, kIrrCnPairMax, P), "plan_irregular failed");
@@ -115,11 +159,12 @@ static void check_irregular(const LdpcCode &L) {
   }
   for (int e = 0; e < L.E; e++) CHECK(P.col_slot[e] == slot_of[L.col_slot[e]], "column edge %d slot", e);
   printf("irregular: plan ok for T=%d, %d slots for %d edges\n", T, P.n_slots, L.E);
+  if (census) irregular_census(L, P, T, census);
 }
 
 // bp_part_kernel: members own whole column / row blocks; every edge's LDS
 // address of the column side is a row slot of the owner or one of its mirrors.
-static void check_partition(const LdpcCode &L) {
+static void check_partition(const LdpcCode &L, bool peg8064 = true) {
   PartitionPlan P;
   CHECK(plan_partition(L, 4, P), "plan_partition failed");
   if (P.vn.empty()) return;
@@ -167,10 +212,47 @@ static void check_partition(const LdpcCode &L) {
       CHECK(has, "column position %d edge %d: row %d of member %d does not hold it", p, k, r, p / NG);
     }
   // the refined cut (layout.cpp PartRefiner; the relabelling alone: 6,602)
-  if (!getenv("KML_PART_REFINE") || getenv("KML_PART_REFINE")[0] != '0')
+  if (peg8064 && (!getenv("KML_PART_REFINE") || getenv("KML_PART_REFINE")[0] != '0'))
     CHECK(P.ncut <= (getenv("KML_PART_REFINE_ITERS") ? 6602 : 5700), "cut %d edges", P.ncut);
   for (int x = 0; x < P.ncut; x++) CHECK(seen_x[x] == 1, "mailbox index %d received %d times", x, seen_x[x]);
+  // the plan fits the kernel (bp_coop.hip part_plan_fits: LDS with 7 dummy
+  // slots, at most 2/3 of the edges cut, 2 x 1024 exchange entries per member)
+  int xmax = 0;
+  for (int m = 0; m < P.G; m++)
+    xmax = std::max(xmax, std::max(P.xr_ptr[m + 1] - P.xr_ptr[m], P.xc_ptr[m + 1] - P.xc_ptr[m]));
+  CHECK(((long long)P.MG * 6 + P.mirror_max + 7) * 16 + L.N <= 160 * 1024, "LDS: mirror_max %d", P.mirror_max);
+  CHECK(3LL * P.ncut <= 2LL * L.E && xmax <= 2 * 1024, "cut %d, exchange list %d", P.ncut, xmax);
   printf("partition: %d of %d edges cut, mirror_max %d\n", P.ncut, L.E, P.mirror_max);
+}
+
+// A code that takes neither specialised plan: a regular code gets no irregular
+// plan (the library makes one for non-regular codes only) and must not be a
+// (3,6) code whose quarters tile the partitioned kernel ((N / 4) % 16 == 0
+// beyond LDS); a non-regular one must be declined by plan_irregular or hold a
+// degree the irregular kernel has no instance for (columns 1..9, rows 2..10).
+// Whatever plan_irregular returns for it, it returns without a fault.
+static void check_none(const LdpcCode &L, const char *name) {
+  bool regular = true, in_range = true;
+  for (int v = 0; v < L.N; v++) {
+    regular &= col_deg(L, v) == L.dv_max;
+    in_range &= col_deg(L, v) >= 1 && col_deg(L, v) <= 9;
+  }
+  for (int r = 0; r < L.M; r++) {
+    regular &= row_deg(L, r) == L.dc_max;
+    in_range &= row_deg(L, r) >= 2 && row_deg(L, r) <= 10;
+  }
+  IrregularPlan P;
+  const bool irr = plan_irregular(L, kIrrThreads, kIrrVnPairMax, kIrrCnPairMax, P);
+  if (regular) {
+    const bool lds = (long long)L.E * 16 + 16 + L.N <= 160 * 1024;
+    CHECK(L.N != 2304, "%s is a PEG2304-class code", name);
+    CHECK(lds || L.dv_max != 3 || L.dc_max != 6 || L.N % 4 || L.M % 4 || (L.N / 4) % 16,
+          "%s tiles the partitioned kernel", name);
+  } else {
+    CHECK(!irr || !in_range, "%s has an irregular plan and degrees the irregular kernel holds", name);
+  }
+  printf("none %s: regular %d, dv_max %d, dc_max %d, plan_irregular %d\n", name, (int)regular, L.dv_max, L.dc_max,
+         (int)irr);
 }
 
 int main(int argc, char **argv) {
@@ -180,6 +262,20 @@ int main(int argc, char **argv) {
   check_regular(a);
   check_irregular(b);
   check_partition(c);
+  for (int i = 4; i + 1 < argc; i += 2) {
+    LdpcCode x;
+    if (!load(x, argv[i + 1], false)) return 2;
+    const char *name = strrchr(argv[i + 1], '/') ? strrchr(argv[i + 1], '/') + 1 : argv[i + 1];
+    if (!strcmp(argv[i], "--irregular")) {
+      check_irregular(x, name);
+    } else if (!strcmp(argv[i], "--partition")) {
+      check_partition(x, false);
+    } else if (!strcmp(argv[i], "--none")) {
+      check_none(x, name);
+    } else {
+      return 2;
+    }
+  }
   printf("plan_errors=%d\n", errors);
   return errors ? 1 : 0;
 }

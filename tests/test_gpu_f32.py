@@ -188,7 +188,7 @@ def test_simulator_path(data_dir):
     ctx.set_precision("f64")
 
 
-@pytest.mark.parametrize("case", ["bg2_qpsk_known", "peg8064_qpsk_known"])
+@pytest.mark.parametrize("case", ["bg2_qpsk_known", "peg8064_qpsk_known", "syn_reg36_192_qpsk_blind"])
 def test_other_codes_refuse_f32(data_dir, case):
     hdr, z = load_case(case)
     assert hdr["active"]

@@ -42,6 +42,7 @@ from conftest import load_case
 pytestmark = pytest.mark.gpu
 
 PEG, PEG8064, BG2 = "PEG2304regular0.5.txt", "PEG8064regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt"
+IRR = "syn_irr1200.txt"  # non-5G irregular, every column degree 1..9 and row degree 2..10 (tests/golden/make_codes.py)
 QPSK, QAM16, QAM64 = "2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"
 # name: matrix, modem, 5G, Es/N0, environment
 CASES = {
@@ -49,6 +50,7 @@ CASES = {
     "peg_qpsk_unfused": (PEG, QPSK, False, 2.0, {"KML_FUSED_DEMAP": "0"}),
     "peg_16qam": (PEG, QAM16, False, 8.0, {}),
     "bg2_16qam": (BG2, QAM16, True, 9.0, {}),  # the oracle fails 61 % of the seed-17 codewords within 8 iterations
+    "syn_irr1200_qpsk": (IRR, QPSK, False, 4.0, {}),  # the PROF instances of the degrees BG2 does not have
 }
 UNSUP = "(code -4)"
 
@@ -150,7 +152,7 @@ def test_per_budget_equality_and_plain_path(env, monkeypatch, case):
     plain = ctx.sim_decode(snr, blind=False)
     cw_err, _, plain_ex = ctx.sim_decode_ex(snr, blind=False)
     prof, cwp, cnt = ctx.sim_decode_profile(snr, blind=False)
-    assert ctx.bp_kernel() == ("bp_irregular_kernel" if is5g else "bp_regular_kernel")
+    assert ctx.bp_kernel() == ("bp_irregular_kernel" if is5g or matrix == IRR else "bp_regular_kernel")
     _check_rows(prof, cwp, err, ret, plain["converged"], P)
     # the ordinary outputs of the profile call are the plain call's
     assert cnt == plain == plain_ex

@@ -290,6 +290,17 @@ def test_bp_golden_vectors(case, data_dir):
     ("PEG8064regular0.5.txt", "2bits_QPSK.txt", False, 1.8, 20, 40),
     ("5GLDPCBG2a3_R12_K960.txt", "2bits_QPSK.txt", True, 1.5, 50, 100),
     ("5GLDPCBG2a3_R12_K960.txt", "6bits_64QAM_Gray.txt", True, 10.0, 50, 60),
+    # the synthetic codes (tests/golden/make_codes.py): every degree instance of
+    # bp_irregular_kernel, the generic bp_kernel's three instances in LDS and
+    # with global slots, bp_part_kernel at NG = 1040; 64QAM at S = 200 and 680
+    ("syn_irr1200.txt", "2bits_QPSK.txt", False, 2.0, 30, 64),
+    ("syn_reg36_192.txt", "2bits_QPSK.txt", False, 3.0, 20, 64),
+    ("syn_reg48_240.txt", "4bit_16QAM_Gray.txt", False, 8.5, 20, 64),
+    ("syn_high120.txt", "2bits_QPSK.txt", False, 2.0, 20, 64),
+    ("syn_reg36_4080.txt", "4bit_16QAM_Gray.txt", False, 6.5, 20, 24),
+    ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, 2.2, 20, 24),
+    ("syn_irr1200.txt", "6bits_64QAM_Gray.txt", False, 10.0, 30, 64),
+    ("syn_reg36_4080.txt", "6bits_64QAM_Gray.txt", False, 10.0, 20, 24),
 ])
 def test_bp_vs_oracle_stream(data_dir, matrix, modem, is5g, snr, max_iter, n):
     """Oracle frames -> oracle P0 -> GPU BP vs oracle BP, bit-exact incl. the
@@ -586,13 +597,34 @@ FAMILY = {"PEG2304regular0.5.txt": "bp_regular_kernel", "5GLDPCBG2a3_R12_K960.tx
           "PEG8064regular0.5.txt": "bp_part_kernel"}
 
 
-@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES)
+# The synthetic codes (tests/golden/make_codes.py), with the constellation and
+# max_iter of their reference fixtures (so the contexts are shared), and the
+# family each must decode on: the generic bp_kernel is the native path of every
+# regular code that is neither PEG2304-class nor tiled by the partitioned kernel.
+SYN_CODES = [("syn_irr1200.txt", "2bits_QPSK.txt", False, 30),       # every degree instance, non-5G
+             ("syn_reg36_192.txt", "2bits_QPSK.txt", False, 20),     # bp_kernel<3,6> in LDS
+             ("syn_reg48_240.txt", "4bit_16QAM_Gray.txt", False, 20),  # bp_kernel<12,12> in LDS, rank-deficient
+             ("syn_high120.txt", "2bits_QPSK.txt", False, 20),       # bp_kernel<32,32> in LDS
+             ("syn_reg36_4080.txt", "4bit_16QAM_Gray.txt", False, 20),  # bp_kernel<3,6>, global slots
+             ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, 20)]    # bp_part_kernel, NG = 1040
+FAMILY.update({"syn_irr1200.txt": "bp_irregular_kernel", "syn_reg36_192.txt": "bp_kernel",
+               "syn_reg48_240.txt": "bp_kernel", "syn_high120.txt": "bp_kernel", "syn_reg36_4080.txt": "bp_kernel",
+               "syn_reg36_4160.txt": "bp_part_kernel"})
+SYN_LARGE = ("syn_reg36_4080.txt", "syn_reg36_4160.txt")
+
+
+@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES + SYN_CODES)
 def test_dispatch_takes_the_specialised_kernel(data_dir, matrix, modem, is5g, max_iter):
     """Each code runs on its own kernel family (so the parity tests below cover
-    all three), not on the generic fallback."""
+    all of them): the shipped codes on the three specialised ones, never on the
+    generic fallback; the synthetic codes on the family they were built for,
+    and only a code with a partition plan reports a partition group."""
     ctx = ctx_for(data_dir, matrix, modem, is5g, max_iter)
     ctx.bp_decode(np.full((2, ctx.cc_len), 0.3), iter_count=2)
     assert ctx.bp_kernel() == FAMILY[matrix]
+    assert ctx.dims["part_group"] == (4 if FAMILY[matrix] == "bp_part_kernel" else 0)
+    if matrix.startswith("syn_"):
+        assert ctx.dims["bp_lds"] == (0 if matrix in SYN_LARGE else 1)
 
 
 @pytest.mark.parametrize("tagged", ["1", "0"])
@@ -652,6 +684,115 @@ def test_partitioned_kernel_deferral_liveness(data_dir, monkeypatch):
         for it in (20, 1, 0):
             ctx.bp_decode(p0, iter_count=it, cc_hat=True, syn=np.zeros((B, ctx.M)))
     ctx.close()
+
+
+def _deferral_batch(ctx, oc, B, family):
+    """FAST codewords beside two outside the fast-division domain (-0.0 and
+    subnormal priors), iteration budgets 20, 1 and 0, bit-exact against the
+    oracle on ret, uu_hat, cc_hat and the soft syndromes."""
+    rng = np.random.default_rng(33)
+    p0 = np.clip(rng.normal(0.5, 0.28, (B, ctx.cc_len)), 0.02, 0.98)
+    p0[7, ::5] = -0.0
+    p0[23, 1::7] = 5e-320
+    for it in (20, 1, 0):
+        r = ctx.bp_decode(p0, iter_count=it, cc_hat=True, syn=np.zeros((B, ctx.M)))
+        assert ctx.bp_kernel() == family
+        for i in list(range(0, B, 5)) + [7, 23, B - 1]:
+            ret, uh, cch, syn = oc.bp_decode(p0[i], it)
+            assert r["ret"][i] == ret, (it, i)
+            assert np.array_equal(r["uu_hat"][i], uh), (it, i)  # it = 0: untouched (zeros) on both sides
+            if it > 0:  # with no iteration the reference's cc_hat_ is whatever its array held: undefined
+                assert np.array_equal(r["cc_hat"][i], cch), (it, i)
+            assert np.array_equal(r["syn"][i], syn, equal_nan=True), (it, i)
+        if it == 0:
+            assert not r["cc_hat"].any()  # the caller's (zero) array, untouched
+
+
+@pytest.mark.parametrize("tagged", ["1", "0"])
+def test_partitioned_kernel_deferral_at_another_tiling(data_dir, monkeypatch, tagged):
+    """The tagged exchange and its deferrals (see the PEG8064 test above) on
+    syn_reg36_4160: NG = 1040 columns and MG = 520 rows per member, so the
+    tails of the 1024 x 2 tiling differ from PEG8064's; B = 96, so some groups
+    take one codeword and some two.  The plan is made at the short annealing
+    schedule (test_host.py checks that it fits there)."""
+    monkeypatch.setenv("KML_PART_TAGGED", tagged)
+    monkeypatch.setenv("KML_PART_REFINE_ITERS", "3000000")
+    ctx = K.Context(matrix_file=os.path.join(data_dir, "syn_reg36_4160.txt"),
+                    modem_file=os.path.join(data_dir, "2bits_QPSK.txt"), is5g=False, active=True, max_iter=20,
+                    device=0)
+    assert ctx.dims["part_group"] == 4
+    _deferral_batch(ctx, oracle_for(data_dir, "syn_reg36_4160.txt", False, 20), 96, "bp_part_kernel")
+    ctx.close()
+
+
+def test_irregular_kernel_deferral_beside_fast_codewords(data_dir):
+    """The same batch on syn_irr1200: FAST codewords beside deferred ones in the
+    irregular kernel's two-launch scheme, on every degree instance."""
+    ctx = ctx_for(data_dir, "syn_irr1200.txt", "2bits_QPSK.txt", False, 30)
+    _deferral_batch(ctx, oracle_for(data_dir, "syn_irr1200.txt", False, 30), 96, "bp_irregular_kernel")
+
+
+@pytest.mark.parametrize("matrix,modem,is5g,max_iter", SYN_CODES)
+def test_counters_with_a_partial_last_word(data_dir, matrix, modem, is5g, max_iter):
+    """K off the 64-bit grid (600, 96, 121, 60, 2040, 2080): the error-count
+    epilogues' partial last word (nb = min(64, K - base)) and the packed
+    reference bits.  Oracle frames loaded as the resident batch; the counters
+    of kml_sim_decode and the per-codeword error bits of kml_sim_decode_ex
+    equal the counts from the oracle's uu_hat."""
+    ctx = ctx_for(data_dir, matrix, modem, is5g, max_iter)
+    oc = oracle_for(data_dir, matrix, is5g, max_iter)
+    om = O.Modem(os.path.join(data_dir, modem))
+    snr = {"syn_irr1200.txt": 2.0, "syn_reg36_192.txt": 3.0, "syn_reg48_240.txt": 8.5, "syn_high120.txt": 2.0,
+           "syn_reg36_4080.txt": 6.5, "syn_reg36_4160.txt": 2.2}[matrix]
+    n = 24 if matrix in SYN_LARGE else 48
+    assert ctx.K % 64 != 0 and ctx.K == oc.K
+    uu, cc, th, y = O.gen_frames(oc, om, snr, n, state=41)
+    uu = uu.astype(np.uint8)
+    errs = np.array([int(np.sum(O.receive(oc, om, y[i], th[i], snr, False)["uu_hat"] != uu[i])) for i in range(n)])
+    assert (errs > 0).any() and (errs == 0).any()  # both kinds of codeword are counted
+    ctx.sim_load(snr, uu, y, th)
+    c = ctx.sim_decode(snr, blind=False)
+    assert ctx.bp_kernel() == FAMILY[matrix]
+    want = dict(err_bit=int(errs.sum()), err_blk=int((errs > 0).sum()), tot_bit=n * ctx.K, tot_blk=n)
+    assert {k: c[k] for k in want} == want
+    cw_err, _, c2 = ctx.sim_decode_ex(snr, blind=False)
+    assert np.array_equal(cw_err, errs)
+    assert {k: c2[k] for k in want} == want
+
+
+def test_degree_above_32_is_refused(data_dir, tmp_path):
+    """A 66 x 33 H with one row of degree 33: no kernel family takes it, the
+    decode raises the dispatcher's message before anything is launched, and
+    the context is destroyed cleanly afterwards."""
+    M, N = 33, 66
+    rows = [sorted({r, (r + 1) % M, M + r}) for r in range(M - 1)]  # M + r: an identity block (full rank)
+    rows.append(sorted(set(range(32)) | {N - 1}))  # degree 33
+    with open(tmp_path / "deg33.txt", "w") as f:
+        f.write(f"num_of_row--num_of_col--rank_of_H\n{M}\t{N}\t{M}\nno_of_row--degree_of_row--no_of_col\n")
+        for r, cols in enumerate(rows):
+            f.write(f"{r} {len(cols)} " + " ".join(map(str, cols)) + " \n")
+    ctx = K.Context(matrix_file=str(tmp_path / "deg33.txt"), modem_file=os.path.join(data_dir, "2bits_QPSK.txt"),
+                    is5g=False, active=True, max_iter=20, device=0)
+    assert ctx.Ncol == N and ctx.M == M
+    with pytest.raises(K.KmlError, match="node degree above 32 is not supported by the BP kernel"):
+        ctx.bp_decode(np.full((2, ctx.cc_len), 0.3), iter_count=2)
+    ctx.close()
+
+
+def test_generic_kernel_on_the_shipped_codes(data_dir):
+    """KML_BP_KERNEL=generic (read once per process, so a fresh child): the
+    generic bp_kernel decodes the reference's vectors of PEG2304 (<3,6> in
+    LDS), BG2 (<12,12>, the punctured-prior branch) and PEG8064 (global slots)
+    bit-exactly: ret, uu_hat, cc_hat and syndrom_soft
+    (tests/generic_kernel_child.py)."""
+    import subprocess
+    import sys
+    from conftest import REPO, TESTS
+    r = subprocess.run([sys.executable, os.path.join(TESTS, "generic_kernel_child.py"), data_dir],
+                       env=dict(os.environ, PYTHONPATH=REPO, KML_BP_KERNEL="generic", KML_PART_REFINE_ITERS="3000000"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert r.stdout.count("bp_kernel ok") == 3, r.stdout
 
 
 @pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES)
@@ -863,6 +1004,13 @@ def test_kmeans_state_adversarial_ties(data_dir, modem):
     ("PEG2304regular0.5.txt", "2bits_QPSK.txt", False),
     ("5GLDPCBG2a3_R12_K960.txt", "4bit_16QAM_Gray.txt", True),
     ("PEG8064regular0.5.txt", "6bits_64QAM_Gray.txt", False),
+    # K % 64 != 0 (600, 96, 121, 60, 2040, 2080): encode_kernel's unaligned path
+    ("syn_irr1200.txt", "2bits_QPSK.txt", False),
+    ("syn_reg36_192.txt", "2bits_QPSK.txt", False),
+    ("syn_reg48_240.txt", "4bit_16QAM_Gray.txt", False),
+    ("syn_high120.txt", "2bits_QPSK.txt", False),
+    ("syn_reg36_4080.txt", "4bit_16QAM_Gray.txt", False),
+    ("syn_reg36_4160.txt", "2bits_QPSK.txt", False),
 ])
 def test_gpu_encoder_equals_host_encoder(data_dir, matrix, modem, is5g):
     """The GPU frame generator's encoder (framegen.hip) equals the host encoder
@@ -870,7 +1018,7 @@ def test_gpu_encoder_equals_host_encoder(data_dir, matrix, modem, is5g):
     nearest constellation point of y / h gives back the transmitted label
     bits (MSB first, modem.cc:12-21), which must be encode(uu)."""
     ctx = ctx_for(data_dir, matrix, modem, is5g)
-    B = 200
+    B = 200 if not matrix.startswith("syn_") else 16 if matrix in SYN_LARGE else 64
     ctx.sim_generate(60.0, B, seed=9, first_cw=77)
     uu, y, h = ctx.sim_frames(B)
     pts = ctx.constellation().reshape(-1, 2)
@@ -990,7 +1138,8 @@ EXACT_MODES = ["KML_NO_FAST", "KML_FORCE_REDO"]
 
 @pytest.mark.parametrize("mode", EXACT_MODES)
 @pytest.mark.parametrize("case", ["peg2304_qpsk_known", "bg2_16qam_known", "peg8064_64qam_known",
-                                  "peg2304_4psk_known_lowsnr"])
+                                  "peg2304_4psk_known_lowsnr", "syn_irr1200_qpsk_known",
+                                  "syn_reg36_4160_qpsk_known"])
 def test_exact_path_golden_vectors(case, data_dir, mode, monkeypatch):
     hdr, z = load_case(case)
     monkeypatch.setenv(mode, "1")

@@ -5,6 +5,7 @@ bit-identical to the oracle, and the exact-math restatements used by the
 device code equal glibc / libgcc on the host."""
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -20,7 +21,25 @@ CODES = [
     ("PEG2304regular0.5.txt", False),
     ("5GLDPCBG2a3_R12_K960.txt", True),
     ("PEG8064regular0.5.txt", False),
+    # the synthetic codes (tests/golden/make_codes.py)
+    ("syn_irr1200.txt", False),
+    ("syn_reg36_192.txt", False),
+    ("syn_reg48_240.txt", False),
+    ("syn_high120.txt", False),
+    ("syn_reg36_4080.txt", False),
+    ("syn_reg36_4160.txt", False),
 ]
+SHIPPED = ("PEG2304regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt", "PEG8064regular0.5.txt")
+# plan_check's extra H files and their roles: the plan each synthetic code takes
+SYN_PLAN_ARGS = [("--irregular", "syn_irr1200.txt"), ("--none", "syn_reg36_192.txt"), ("--none", "syn_reg48_240.txt"),
+                 ("--none", "syn_high120.txt"), ("--none", "syn_reg36_4080.txt"), ("--partition", "syn_reg36_4160.txt")]
+
+
+def plan_check_args(data_dir):
+    return [os.path.join(data_dir, f) for f in SHIPPED] + [a for role, f in SYN_PLAN_ARGS
+                                                           for a in (role, os.path.join(data_dir, f))]
+
+
 MODEMS = ["2bits_QPSK.txt", "2bits_4PSK.txt", "4bit_16QAM_Gray.txt", "4bit_16QAM_phi1.txt", "4bit_16QAM_phi2.txt",
           "6bits_64QAM_Gray.txt"]
 
@@ -54,6 +73,8 @@ def test_planner_matches_oracle(data_dir, matrix, is5g, active):
     oc = oracle_code(data_dir, matrix, is5g, active)
     assert (ctx.M, ctx.Ncol, ctx.K, ctx.cc_len, ctx.Z, ctx.E, ctx.chk) == (oc.M, oc.N, oc.K, oc.cc_len, oc.Z, oc.E,
                                                                            oc.chk)
+    if matrix == "syn_reg48_240.txt" and active:  # rank-deficient: the (4,8) rows sum to zero
+        assert ctx.chk == 119 and ctx.K == 121
     assert np.array_equal(ctx.perm(), oc.perm())
     for a, b in zip(ctx.graph(), oc.graph()):
         assert np.array_equal(a, b)
@@ -194,17 +215,37 @@ def test_kernel_placement_plans(tmp_path, data_dir):
     """The lane / slot placement plans the kernels rely on (layout.cpp), on the
     reference's H files: bp_regular's interleaved row slots and c2v halves,
     bp_irregular's paired rounds (each column / row once, pairs of one degree
-    within the limits, one degree per paired wave), bp_part's partition."""
+    within the limits, one degree per paired wave), bp_part's partition; and
+    on the synthetic codes in the role each was built for (an irregular plan, a
+    partition plan, or neither)."""
     exe = tmp_path / "planc"
     csrc = os.path.join(REPO, "kmldpc_amd", "csrc")
     subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I", csrc, "-o", str(exe),
                     os.path.join(REPO, "tests", "native", "plan_check.cpp"), os.path.join(csrc, "code.cpp"),
                     os.path.join(csrc, "layout.cpp")], check=True)
-    out = subprocess.run([str(exe)] + [os.path.join(data_dir, f) for f in
-                                       ("PEG2304regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt", "PEG8064regular0.5.txt")],
-                         capture_output=True, text=True)
+    out = subprocess.run([str(exe)] + plan_check_args(data_dir), capture_output=True, text=True)
     assert out.returncode == 0, out.stdout
     assert "plan_errors=0" in out.stdout
+    # syn_irr1200 is built to reach what BG2's plan never does: the census of its plan
+    with open(os.path.join(data_dir, "syn_irr1200.txt")) as f:
+        rows = [ln.split() for ln in f.read().splitlines()[3:]]
+    assert {int(r[1]) for r in rows} == set(range(2, 11))  # every row degree 2..10
+    assert set(np.bincount([int(c) for r in rows for c in r[2:]])) == set(range(1, 10))  # every column degree 1..9
+    census = {}
+    for ln in out.stdout.splitlines():
+        m = re.fullmatch(r"census syn_irr1200\.txt (vn|cn): paired \{([\d,]*)\} single \{([\d,]*)\} mixed (\d+) "
+                         r"idle (\d+) partial_pair (\d+)", ln)
+        if m:
+            ints = lambda t: {int(x) for x in t.split(",") if x}
+            census[m[1]] = dict(paired=ints(m[2]), single=ints(m[3]), mixed=int(m[4]), idle=int(m[5]),
+                                partial=int(m[6]))
+    assert set(census) == {"vn", "cn"}, out.stdout
+    assert census["vn"]["paired"] | census["vn"]["single"] == set(range(1, 10))
+    assert census["cn"]["paired"] | census["cn"]["single"] == set(range(2, 11))
+    assert {2, 3, 7} <= census["cn"]["paired"] and {3, 7, 9} <= census["cn"]["single"]
+    assert {6, 8} <= census["vn"]["single"]
+    for phase in ("vn", "cn"):  # a mixed wave, an idle wave and a partial pair wave in each phase
+        assert census[phase]["mixed"] >= 1 and census[phase]["idle"] >= 1 and census[phase]["partial"] >= 1, phase
 
 
 def test_host_code_under_sanitizers(tmp_path, data_dir):
@@ -213,7 +254,11 @@ def test_host_code_under_sanitizers(tmp_path, data_dir):
     AddressSanitizer + UndefinedBehaviorSanitizer: the placement-plan checks on
     the reference's H files, encoded codewords with a zero syndrome, and the
     error paths on truncated / garbage H and constellation files and broken
-    TOML (tests/native/host_san_check.cpp).  Any sanitizer finding aborts."""
+    TOML (tests/native/host_san_check.cpp).  Any sanitizer finding aborts.
+    The synthetic codes run beside the reference's, in their roles; this run is
+    also where syn_reg36_4160's partition plan is shown to fit the kernel at
+    the short annealing schedule that its GPU deferral test creates contexts
+    with (plan_check.cpp check_partition)."""
     csrc = os.path.join(REPO, "kmldpc_amd", "csrc")
     flags = ["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
              "-fno-omit-frame-pointer", "-I", csrc]
@@ -233,11 +278,11 @@ def test_host_code_under_sanitizers(tmp_path, data_dir):
     out = subprocess.run([str(hsc), data_dir, str(scratch)], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr[-4000:]
     assert "san_errors=0" in out.stdout
-    out = subprocess.run([str(planc)] + [os.path.join(data_dir, f) for f in
-                                         ("PEG2304regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt", "PEG8064regular0.5.txt")],
-                         capture_output=True, text=True, env=env, timeout=600)
+    out = subprocess.run([str(planc)] + plan_check_args(data_dir), capture_output=True, text=True, env=env,
+                         timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr[-4000:]
     assert "plan_errors=0" in out.stdout
+    assert out.stdout.count("partition: ") == 2 and out.stdout.count("census syn_irr1200.txt") == 2, out.stdout
 
 
 def test_cn_division_tail_exact_near_one():
