@@ -27,48 +27,43 @@ __device__ __forceinline__ void lds_st(unsigned a, T v) {
   *(__attribute__((address_space(3))) T *)(size_t)a = v;
 }
 
-// Workgroup OR of a predicate with one barrier: each wave's lane 0 stores the
-// wave's ballot to its own LDS word, and after the barrier every lane ORs the
-// NW words (vector loads).  (__syncthreads_or goes through a two-barrier
-// library reduction: ~650 more cycles per call at 12 waves.)  The words need
-// no reset: a wave rewrites its word only after a later barrier that every
-// reader of the previous values has passed — callers must place one between
-// two calls (the BP kernels' VN-phase barrier).
+// Workgroup OR of one or two predicates with one barrier.  Each wave keeps one
+// LDS BYTE in a 16-byte aligned array (WgVotes): lane 0 stores (any p0) |
+// (any p1) << 1 straight from the ballots, and after the barrier every wave
+// fetches the NW bytes with ONE LDS read (b32 ... b128; b96 at 12 waves, so the
+// bytes of absent waves are never read and need no initialisation), ORs the
+// dwords, moves the word to a scalar register (every lane read the same
+// address) and tests the byte lanes there: bit 0 of the result = OR of p0,
+// bit 1 = OR of p1.  The predicates are bool so that a compare's lane mask
+// feeds the ballot as it is.  (__syncthreads_or goes through a two-barrier
+// library reduction: ~650 more cycles per call at 12 waves; the earlier form
+// of these helpers, one dword per wave, read three b128 and folded them with
+// eleven dependent v_or.)  The bytes need no reset: a wave rewrites its byte
+// only after a later barrier that every reader of the previous values has
+// passed — callers must place one between two calls on the same array (the BP
+// kernels' VN-phase barrier).
+struct alignas(16) WgVotes {
+  unsigned w[4];
+};
 template <int NW>
-__device__ __forceinline__ int wg_any(int pred, int *wflags) {
-  static_assert(NW % 4 == 0 && NW <= 16, "wave flags are read as int4");
-  const int any = __ballot(pred) != 0;
-  if ((threadIdx.x & 63) == 0) wflags[threadIdx.x >> 6] = any;
+__device__ __forceinline__ int wg_any2(bool p0, bool p1, WgVotes &votes) {
+  static_assert(NW % 4 == 0 && NW <= 16, "wave votes are read as NW / 4 dwords");
+  const unsigned any = (__ballot(p0) != 0 ? 1u : 0u) | (__ballot(p1) != 0 ? 2u : 0u);
+  if ((threadIdx.x & 63) == 0) reinterpret_cast<unsigned char *>(votes.w)[threadIdx.x >> 6] = (unsigned char)any;
   __syncthreads();
-  int r = 0;
+  unsigned r = 0;
 #pragma unroll
-  for (int w = 0; w < NW; w += 4) {
-    const int4 v = *reinterpret_cast<const int4 *>(wflags + w);
-    r |= v.x | v.y | v.z | v.w;
-  }
-  return r;
+  for (int w = 0; w < NW / 4; ++w) r |= votes.w[w];
+  r = (unsigned)__builtin_amdgcn_readfirstlane((int)r);
+  return ((r & 0x01010101u) ? 1 : 0) | ((r & 0x02020202u) ? 2 : 0);
 }
-
-// Two workgroup ORs with one barrier (same rules as wg_any): bit 0 = OR of
-// p0, bit 1 = OR of p1.
 template <int NW>
-__device__ __forceinline__ int wg_any2(int p0, int p1, int *wflags) {
-  static_assert(NW % 4 == 0 && NW <= 16, "wave flags are read as int4");
-  const int any = (__ballot(p0) != 0 ? 1 : 0) | (__ballot(p1) != 0 ? 2 : 0);
-  if ((threadIdx.x & 63) == 0) wflags[threadIdx.x >> 6] = any;
-  __syncthreads();
-  int r = 0;
-#pragma unroll
-  for (int w = 0; w < NW; w += 4) {
-    const int4 v = *reinterpret_cast<const int4 *>(wflags + w);
-    r |= v.x | v.y | v.z | v.w;
-  }
-  return r;
+__device__ __forceinline__ int wg_any(bool pred, WgVotes &votes) {
+  return wg_any2<NW>(pred, false, votes) & 1;
 }
-
 template <int NW>
-__device__ __forceinline__ int wg_all(int pred, int *wflags) {
-  return !wg_any<NW>(!pred, wflags);
+__device__ __forceinline__ bool wg_all(bool pred, WgVotes &votes) {
+  return !wg_any<NW>(!pred, votes);
 }
 
 // hipcc's reciprocal refinement of an f64 '/': v_rcp_f64 and two Newton steps.

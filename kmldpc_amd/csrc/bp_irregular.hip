@@ -373,7 +373,7 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
   auto pbase = [](unsigned w) { return (int)(w & 0x3FFFu); };
   auto pdeg = [](unsigned w) { return (int)((w >> 14) & 15u); };
   auto pitem = [](unsigned w) { return (int)(w >> 18); };
-  __shared__ __attribute__((aligned(16))) int wflags[16];  // wg_any (bp_common.hpp)
+  __shared__ WgVotes wflags;  // wg_any (bp_common.hpp)
   int iter = 0;
   bool conv = false, sus = sus0;
   auto prior = [&](int v) { return v >= c.punct ? p0s[v - c.punct] : 0.5; };  // :126-134
@@ -446,13 +446,12 @@ __device__ __forceinline__ bool decode_irr(const DevCode &c, const BpLaunch &a, 
       sv[2] = s1[0];
       par[2] = p1[0];
     }
-    int fail = 0;
+    // the pair's halves of the three rows in one word, one swap for the lot
+    // (a row the pair does not have keeps par = 0 in both lanes)
+    unsigned pw = par[0] >> 31;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const int p = (int)(par[r] >> 31);
-      const int full = p ^ swap_pair_i(p);
-      if (cp[r] != ~0u) fail |= full;
-    }
+    for (int r = 1; r < 3; ++r) pw = __builtin_amdgcn_alignbit(pw, par[r], 31);
+    const bool fail = pw != (unsigned)swap_pair_i((int)pw);
     IRR_STAMP(5);
     const int wg = FAST ? wg_any2<T / 64>(fail, sus, wflags) : wg_any<T / 64>(fail, wflags);
     if (FAST && (wg & 2)) {  // an unproven quotient in this VN phase: redo exactly
@@ -488,7 +487,7 @@ template <int T, bool SYN, bool EXACT, bool PROF = false>
 __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, unsigned int *queue, int fast_allowed) {
   const double plo = fast_prior_lo(c.dv_max);  // FAST prior domain (bp_common.hpp)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) int pflags[16];  // wg_all of the FAST prior check (bp_common.hpp)
+  __shared__ WgVotes pflags;  // wg_all of the FAST prior check (bp_common.hpp)
   // PROF: the codeword's reference words and its error bits per iteration, and
   // the workgroup's sums per budget {err_bit, err_blk, converged} (lane k alone
   // touches wprof[k]; flushed at the exit)
@@ -541,7 +540,7 @@ __global__ __launch_bounds__(T) void bp_irregular_kernel(DevCode c, BpLaunch a, 
       ok = ok && fast_prior_ok(q, plo);
     }
     for (int e = tid; e < c.irr_slots; e += T) slots[e].x = 0.5;  // InitMsg
-    const bool fast = wg_all<T / 64>(ok ? 1 : 0, pflags) && (fast_allowed & 1);
+    const bool fast = wg_all<T / 64>(ok, pflags) && (fast_allowed & 1);
 
     int iter = 0;
     bool conv = false;

@@ -22,8 +22,12 @@
 //   * the early-stop parity check rides on the CN phase: the VN phase leaves
 //     each column's decision in the sign bit of its q1 words, each lane XORs
 //     the ones of its half-row as its chain loads them, and the pair combines
-//     the halves through the same DPP swap; the workgroup OR is one barrier
-//     (bp_common.hpp wg_any).
+//     the halves of its RC rows, packed into one word, through one DPP swap;
+//     the workgroup OR is one barrier, one LDS byte per wave going in and one
+//     LDS read and a scalar test coming out (bp_common.hpp wg_any2).  Measured
+//     against the dword-per-wave vote it replaced, same box: the last waves'
+//     wait at the CN phase's closing barrier 585 -> 400 cycles per phase,
+//     8.59 -> 8.44 ms per step (-1.7%; profiles/r08_ab_headline_summary.txt).
 //   * wave priorities: falling by step in the VN phase, by wave age in the CN
 //     phase (kCnAgePrio).
 //   * LDS placement (layout.hpp): the columns' lane assignment is annealed on
@@ -175,7 +179,7 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
                                            int *perr = nullptr) {
   static_assert(DC % 2 == 0, "the lane-pair split assumes an even row degree");
   constexpr int H = DC / 2;
-  __shared__ __attribute__((aligned(16))) int wflags[16];  // wg_any (bp_common.hpp)
+  __shared__ WgVotes wflags;  // wg_any (bp_common.hpp)
   int iter = 0;
   bool conv = false, sus = sus0;
 #if KML_STAMPS
@@ -382,12 +386,13 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
 #pragma unroll
       for (int r = 0; r < RC; ++r) syn0[r] = s0[r];
     }
-    int fail = 0;
+    // the pair's halves of all RC rows in one word (row r's sign bit ends up at
+    // bit RC-1-r: each alignbit shifts the word left and brings the next row's
+    // bit 31 in at bit 0), one swap for the lot
+    unsigned pw = par[0] >> 31;
 #pragma unroll
-    for (int r = 0; r < RC; ++r) {
-      const int p = (int)(par[r] >> 31);
-      fail |= p ^ swap_pair_i(p);
-    }
+    for (int r = 1; r < RC; ++r) pw = __builtin_amdgcn_alignbit(pw, par[r], 31);
+    const bool fail = pw != (unsigned)swap_pair_i((int)pw);
     REG_WSTAMP(2);
     const int wg = FAST ? wg_any2<T / 64>(fail, sus, wflags) : wg_any<T / 64>(fail, wflags);
     REG_WSTAMP(3);
@@ -436,7 +441,7 @@ template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT, 
 __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, unsigned int *queue, int fast_allowed) {
   const double plo = fast_prior_lo(c.dv_max);  // FAST prior domain (bp_common.hpp)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) int pflags[16];  // wg_all of the FAST prior check (bp_common.hpp)
+  __shared__ WgVotes pflags;  // wg_all of the FAST prior check (bp_common.hpp)
   // fused demap: the constellation and the exp table in LDS (demap_common.hpp)
   __shared__ double dcons[DMB > 0 ? (2 << DMB) : 2];
   __shared__ uint64_t detab[DMB > 0 ? 256 : 1];
@@ -550,7 +555,7 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
     }
     // the LDS writes land before wave 0 passes the next barrier (the barriers wait lgkmcnt only)
     if (ref_pre) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const bool fast = wg_all<T / 64>(ok ? 1 : 0, pflags) && (fast_allowed & 1);
+    const bool fast = wg_all<T / 64>(ok, pflags) && (fast_allowed & 1);
     REG_STAMP(2);
 
     int iter = 0;

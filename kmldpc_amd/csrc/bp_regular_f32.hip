@@ -81,8 +81,8 @@ __global__ __launch_bounds__(T) void bp_regular_f32_kernel(DevCode c, BpLaunch a
   static_assert(DC % 2 == 0, "the lane-pair split assumes an even row degree");
   constexpr int H = DC / 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) int wflags[16];  // wg_any (bp_common.hpp)
-  __shared__ __attribute__((aligned(16))) int pflags[16];  // wg_all of the fused demap's proof
+  __shared__ WgVotes wflags;  // wg_any (bp_common.hpp)
+  __shared__ WgVotes pflags;  // wg_all of the fused demap's proof
   __shared__ double dcons[DMB > 0 ? (2 << DMB) : 2];
   __shared__ uint64_t detab[DMB > 0 ? 256 : 1];
   __shared__ uint64_t refw[kF32MaxKw];                    // this codeword's reference bits
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(T) void bp_regular_f32_kernel(DevCode c, BpLaunch a
     // every prior is in registers before the first slot store (p0s aliases the slots)
     bool defer = false;
     if constexpr (DMB > 0 && !EXACT)
-      defer = !wg_all<T / 64>(dok ? 1 : 0, pflags);
+      defer = !wg_all<T / 64>(dok, pflags);
     else if constexpr (DMB > 0)
       __syncthreads();
     if (defer) {  // (DMB > 0, FAST demap) the EXACT launch demaps and decodes this codeword
@@ -310,12 +310,11 @@ __global__ __launch_bounds__(T) void bp_regular_f32_kernel(DevCode c, BpLaunch a
 #pragma unroll
         for (int r = 0; r < RC; ++r) syn0[r] = s[r].x;
       }
-      int fail = 0;
+      // the pair's halves of all RC rows in one word, one swap for the lot (bp_regular.hip)
+      unsigned pw = par[0] >> 31;
 #pragma unroll
-      for (int r = 0; r < RC; ++r) {
-        const int p = (int)(par[r] >> 31);
-        fail |= p ^ swap_pair_i32(p);
-      }
+      for (int r = 1; r < RC; ++r) pw = __builtin_amdgcn_alignbit(pw, par[r], 31);
+      const bool fail = pw != (unsigned)swap_pair_i32((int)pw);
       if (!wg_any<T / 64>(fail, wflags)) {  // every row satisfied before this CN phase
         conv = true;
         break;
