@@ -31,13 +31,13 @@
 #include <cstdlib>
 
 #include "bp_common.hpp"
+#include "bp_launch.hpp"
 #include "kernels.hpp"
 
 namespace kml {
 
 namespace {
 
-constexpr int kLdsBytes = 160 * 1024;
 constexpr int kRedBytes = 16;
 
 template <int T>
@@ -261,25 +261,16 @@ template <int DV, int DC, bool LDS, bool SYN>
 hipError_t launch_t(const DevCode &c, const BpLaunch &a, unsigned int *queue, hipStream_t s) {
   auto kern = bp_kernel<DV, DC, LDS, SYN, kThreads>;
   const size_t lds = LDS ? (size_t)c.E * 16 + kRedBytes + (size_t)c.N : kRedBytes + (size_t)c.N;
-  hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // the occupancy query runs with the dynamic-LDS limit already raised, as it
+  // always has here (launch_persistent sets the attribute again: harmless)
+  hipError_t e = set_dynamic_lds((const void *)kern, lds);
   if (e != hipSuccess) return e;
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   int per_cu = 1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kThreads, lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
-  long long grid = (long long)ncu * per_cu;
-  if (!LDS) {
-    const long long cap = a.gslots_cap / (c.E > 0 ? c.E : 1);
-    if (grid > cap) grid = cap;
-    if (grid < 1) return hipErrorInvalidValue;
-  }
-  if (grid > a.B) grid = a.B;
-  e = hipMemsetAsync(queue, 0, sizeof(unsigned int), s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, s, c, a, queue);
-  return hipGetLastError();
+  // global-slot mode: one slot array per workgroup, as many as the workspace holds
+  const long long cap = LDS ? kNoGridCap : a.gslots_cap / (c.E > 0 ? c.E : 1);
+  return launch_persistent(kern, kThreads, lds, per_cu, cap, false, a, s, c, a, queue);
 }
 
 template <bool LDS, bool SYN>
@@ -305,7 +296,7 @@ int kernel_variant() {
 }
 }  // namespace
 
-bool bp_uses_lds(const DevCode &c) { return (long long)c.E * 16 + kRedBytes + c.N <= kLdsBytes; }
+bool bp_uses_lds(const DevCode &c) { return (long long)c.E * 16 + kRedBytes + c.N <= (long long)kLdsLimit; }
 
 const char *bp_profile_refusal(const DevCode &c, int iter_count) {
   if (iter_count > kBpProfMaxIter) return "the iteration profile supports max_iter <= 64";
@@ -327,10 +318,7 @@ const char *bp_profile_refusal(const DevCode &c, int iter_count) {
 
 long long bp_gslots_needed(const DevCode &c) {
   if (bp_uses_lds(c)) return 0;
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  return (long long)ncu * 4 * c.E;  // up to 4 resident workgroups per CU
+  return (long long)device_cus() * 4 * c.E;  // up to 4 resident workgroups per CU
 }
 
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family) {
@@ -361,47 +349,36 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
     if (family) *family = "bp_regular_f32_kernel";
     return e;
   }
-  if (a.cw_prof || a.prof) {
-    // the iteration profile lives in the regular and the irregular LDS kernels
-    // only: their PROF instances or an error, never another family
-    const char *why = bp_profile_refusal(c, a.iter_count);
-    hipError_t e = why ? hipErrorNotSupported : launch_bp_regular(c, a, s);
-    if (!why && e != hipErrorNotSupported) {
-      if (family) *family = "bp_regular_kernel";
-      return e;
+  // the iteration profile lives in the regular and the irregular LDS kernels
+  // only: their PROF instances or an error, never another family
+  const bool profile = a.cw_prof || a.prof;
+  if (profile)
+    if (const char *why = bp_profile_refusal(c, a.iter_count)) {
+      if (err) *err = why;
+      return hipErrorNotSupported;
     }
-    if (!why) e = launch_bp_irregular(c, a, s);
-    if (!why && e != hipErrorNotSupported) {
-      if (family) *family = "bp_irregular_kernel";
-      return e;
-    }
-    if (err) *err = why ? why : "the iteration profile is not available for this code or launch";
-    return hipErrorNotSupported;
-  }
   const bool lds = bp_uses_lds(c);
   // kernel families, most specialised first: regular PEG2304-class (LDS),
   // irregular with degrees <= 9 / 10 (LDS), cooperative regular (L2), generic
-  const int variant = kernel_variant();  // 0 auto, 1 generic
-  if (lds && variant == 0) {
-    hipError_t e = launch_bp_regular(c, a, s);
-    if (e != hipErrorNotSupported) {
-      if (family) *family = "bp_regular_kernel";
-      return e;
+  const struct {
+    bool applies, profiles;
+    hipError_t (*launch)(const DevCode &, const BpLaunch &, hipStream_t);
+    const char *name;
+  } families[] = {{lds, true, launch_bp_regular, "bp_regular_kernel"},
+                  {lds, true, launch_bp_irregular, "bp_irregular_kernel"},
+                  {!lds, false, launch_bp_coop, bp_coop_family(c)}};
+  if (kernel_variant() == 0)  // 0 auto, 1 generic
+    for (const auto &f : families) {
+      if (!f.applies || (profile && !f.profiles)) continue;
+      const hipError_t e = f.launch(c, a, s);
+      if (e != hipErrorNotSupported) {
+        if (family) *family = f.name;
+        return e;
+      }
     }
-  }
-  if (lds && variant == 0) {
-    hipError_t e = launch_bp_irregular(c, a, s);
-    if (e != hipErrorNotSupported) {
-      if (family) *family = "bp_irregular_kernel";
-      return e;
-    }
-  }
-  if (!lds && variant == 0) {
-    hipError_t e = launch_bp_coop(c, a, s);
-    if (e != hipErrorNotSupported) {
-      if (family) *family = bp_coop_family(c);
-      return e;
-    }
+  if (profile) {
+    if (err) *err = "the iteration profile is not available for this code or launch";
+    return hipErrorNotSupported;
   }
   if (!lds && (a.gslots == nullptr || a.gslots_cap < c.E)) {
     if (err) *err = "global slot workspace missing";

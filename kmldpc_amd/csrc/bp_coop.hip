@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "bp_common.hpp"
+#include "bp_launch.hpp"
 #include "kernels.hpp"
 
 namespace kml {
@@ -1182,12 +1183,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1))) void bp_
 hipError_t launch_resident(const void *kern, unsigned grid, unsigned block, void **args, unsigned lds, hipStream_t s) {
   if (const char *e = getenv("KML_COOP_LAUNCH"))
     if (e[0] == '0') {
-      int per_cu = 0, dev = 0, ncu = 0;
+      int per_cu = 0;
       hipError_t r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)block, lds);
       if (r != hipSuccess) return r;
-      hipGetDevice(&dev);
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-      if ((long long)per_cu * ncu < (long long)grid) return hipErrorCooperativeLaunchTooLarge;
+      if ((long long)per_cu * device_cus() < (long long)grid) return hipErrorCooperativeLaunchTooLarge;
       return hipLaunchKernel(kern, dim3(grid), dim3(block), args, lds, s);
     }
   return hipLaunchCooperativeKernel(kern, dim3(grid), dim3(block), args, lds, s);
@@ -1197,9 +1196,9 @@ template <int kG, int T, int RV, int RC, int RX, bool SYN, bool TAGGED, bool EXA
 hipError_t launch_part_t(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast, int groups, bool reset_abort) {
   auto kern = bp_part_kernel<kG, T, RV, RC, RX, SYN, TAGGED, EXACT>;
   const size_t lds = part_lds_bytes(c);
-  hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = set_dynamic_lds((const void *)kern, lds);
   if (e != hipSuccess) return e;
-  e = hipMemsetAsync(a.queue, 0, sizeof(unsigned int), s);
+  e = reset_queue(a, s);
   if (e != hipSuccess) return e;
   // the group blocks, and the abort word unless this launch follows one whose abort must persist
   e = hipMemsetAsync(a.gsync, 0, sizeof(GroupSync) * (size_t)groups + (reset_abort ? 2 * sizeof(unsigned) : 0), s);
@@ -1225,25 +1224,25 @@ hipError_t launch_part_t(const DevCode &c, const BpLaunch &a, hipStream_t s, int
 template <int kG, int T_, int R_, int X_, bool SYN>
 hipError_t launch_part_chain(const DevCode &c, const BpLaunch &a, const BpLaunch &d, hipStream_t s, int fast, int groups,
                              bool tagged) {
-  if (!(fast & 1)) return launch_part_t<kG, T_, R_, R_, X_, SYN, false, true>(c, a, s, 0, groups, a.reset_abort);
-  if (!a.defer_idx || !a.defer_cnt) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(a.defer_cnt, 0, sizeof(unsigned), s);
-  if (e != hipSuccess) return e;
-  BpLaunch bf = a;  // barrier-exchange FAST launch: the whole batch, or the tagged launch's deferrals
-  bool reset = a.reset_abort;
-  if (tagged) {
-    e = launch_part_t<kG, T_, R_, R_, X_, SYN, true, false>(c, d, s, fast, groups, reset);
-    if (e != hipSuccess) return e;
-    bf.cw_idx = d.defer_idx;
-    bf.B_dev = d.defer_cnt;
-    reset = false;  // an abort of an earlier launch stays visible
-  }
-  e = launch_part_t<kG, T_, R_, R_, X_, SYN, false, false>(c, bf, s, fast, groups, reset);
-  if (e != hipSuccess) return e;
-  BpLaunch be = a;  // exact launch over what the FAST launches deferred
-  be.cw_idx = a.defer_idx;
-  be.B_dev = a.defer_cnt;
-  return launch_part_t<kG, T_, R_, R_, X_, SYN, false, true>(c, be, s, 0, groups, false);
+  auto exact = [&](const BpLaunch &b, bool reset) {
+    return launch_part_t<kG, T_, R_, R_, X_, SYN, false, true>(c, b, s, 0, groups, reset);
+  };
+  if (!(fast & 1)) return exact(a, a.reset_abort);
+  // the FAST step: the tagged launch and the barrier-exchange launch over its
+  // deferrals, or the barrier-exchange launch over the whole batch
+  auto fast_launches = [&](const BpLaunch &b) {
+    BpLaunch bf = b;
+    bool reset = b.reset_abort;
+    if (tagged) {
+      hipError_t e = launch_part_t<kG, T_, R_, R_, X_, SYN, true, false>(c, d, s, fast, groups, reset);
+      if (e != hipSuccess) return e;
+      bf.cw_idx = d.defer_idx;
+      bf.B_dev = d.defer_cnt;
+      reset = false;  // an abort of an earlier launch stays visible
+    }
+    return launch_part_t<kG, T_, R_, R_, X_, SYN, false, false>(c, bf, s, fast, groups, reset);
+  };
+  return launch_fast_then_exact(a, s, fast_launches, [&](const BpLaunch &b) { return exact(b, false); });
 }
 
 }  // namespace
@@ -1251,18 +1250,18 @@ hipError_t launch_part_chain(const DevCode &c, const BpLaunch &a, const BpLaunch
 size_t bp_coop_sync_bytes(int groups) { return part_defer_offset(groups) + 16; }
 
 int bp_part_group_size(int N, int M, int E, int dv_max, int dc_max, int regular) {
-  if (!regular || dv_max != 3 || dc_max != 6 || (long long)E * 16 + 16 + N <= 160 * 1024) return 0;
+  if (!regular || dv_max != 3 || dc_max != 6 || (size_t)E * 16 + 16 + (size_t)N <= kLdsLimit) return 0;
   const int G = kPartG;
   if (N % G || M % G || (N / G) % 16) return 0;
   // tilings up to 2048 columns and half-rows per member; the LDS check
   // including the mirror slots is part_plan_fits (after planning)
   const int NG = N / G, MG = M / G;
-  return ((long long)MG * 6 * 16 + N <= 160 * 1024 && NG <= 2048 && 2 * MG <= 2048) ? G : 0;
+  return ((size_t)MG * 6 * 16 + (size_t)N <= kLdsLimit && NG <= 2048 && 2 * MG <= 2048) ? G : 0;
 }
 
 bool part_plan_fits(int G, int N, int M, int E, int ncut, int mirror_max, int xmax) {
   const long long lds = ((long long)M / G * 6 + mirror_max + kPartDummy) * 16 + N;
-  return G == kPartG && lds <= 160 * 1024 && 3LL * ncut <= 2LL * E && xmax <= 2 * 1024;
+  return G == kPartG && lds <= (long long)kLdsLimit && 3LL * ncut <= 2LL * E && xmax <= 2 * 1024;
 }
 
 // Codes without a partition plan (or whose plan did not fit) decode on the
@@ -1270,10 +1269,7 @@ bool part_plan_fits(int G, int N, int M, int E, int ncut, int mirror_max, int xm
 int bp_coop_groups(const DevCode &c) {
   if (!c.regular || !c.reg_pos || c.dv_max != 3 || c.dc_max != 6 || bp_uses_lds(c)) return 0;
   if (c.pt_G != kPartG || c.pt_vn == nullptr) return 0;
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  return (ncu / (8 * kPartG)) * 8;  // 8 XCDs, groups of 4 per XCD
+  return (device_cus() / (8 * kPartG)) * 8;  // 8 XCDs, groups of 4 per XCD
 }
 
 #if KML_STAMPS

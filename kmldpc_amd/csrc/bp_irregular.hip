@@ -35,6 +35,7 @@
 //   * the shared-reciprocal exact division (bp_common.hpp) on codewords whose
 //     priors qualify.
 #include "bp_common.hpp"
+#include "bp_launch.hpp"
 #include "kernels.hpp"
 
 namespace kml {
@@ -631,52 +632,28 @@ size_t irr_lds_bytes(const DevCode &c) {
 template <int T, bool SYN, bool EXACT, bool PROF = false>
 hipError_t launch_irr_one(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
   auto kern = bp_irregular_kernel<T, SYN, EXACT, PROF>;
-  const size_t lds = irr_lds_bytes(c);
-  hipError_t e;
-  if constexpr (PROF) {  // the profile's static LDS counts against the same limit
-    hipFuncAttributes fa;
-    e = hipFuncGetAttributes(&fa, (const void *)kern);
-    if (e != hipSuccess) return e;
-    if (lds + fa.sharedSizeBytes > 160 * 1024) return hipErrorNotSupported;
-  }
-  e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  long long grid = ncu;
-  if (grid > a.B) grid = a.B;
-  e = hipMemsetAsync(a.queue, 0, sizeof(unsigned int), s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T), lds, s, c, a, a.queue, fast_allowed);
-  return hipGetLastError();
+  return launch_persistent(kern, T, irr_lds_bytes(c), 1, kNoGridCap, PROF, a, s, c, a, a.queue, fast_allowed);
 }
 
-// FAST kernel, then the exact kernel over its defer list (bp_regular.hip launch_reg_t)
+// FAST kernel, then the exact kernel over its defer list; with FAST division
+// off, the exact kernel over the batch.
 template <int T, bool SYN, bool PROF = false>
 hipError_t launch_irr_t(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
   if (!(fast_allowed & 1)) return launch_irr_one<T, SYN, true, PROF>(c, a, s, 0);
-  if (!a.defer_idx || !a.defer_cnt) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(a.defer_cnt, 0, sizeof(unsigned), s);
-  if (e != hipSuccess) return e;
-  e = launch_irr_one<T, SYN, false, PROF>(c, a, s, fast_allowed);
-  if (e != hipSuccess) return e;
-  BpLaunch b = a;
-  b.cw_idx = a.defer_idx;
-  b.B_dev = a.defer_cnt;
-  return launch_irr_one<T, SYN, true, PROF>(c, b, s, 0);
+  return launch_fast_then_exact(
+      a, s, [&](const BpLaunch &b) { return launch_irr_one<T, SYN, false, PROF>(c, b, s, fast_allowed); },
+      [&](const BpLaunch &b) { return launch_irr_one<T, SYN, true, PROF>(c, b, s, 0); });
 }
 
 }  // namespace
 
 hipError_t launch_bp_irregular(const DevCode &c, const BpLaunch &a, hipStream_t s) {
   constexpr int T = kIrrThreads;
-  if (irr_lds_bytes(c) > 160 * 1024 || c.irr_slots > 16383) return hipErrorNotSupported;
+  if (irr_lds_bytes(c) > kLdsLimit || c.irr_slots > 16383) return hipErrorNotSupported;
   if (!c.irr_ok || !c.irr_vn) return hipErrorNotSupported;
   const int fast = bp_fast_mode(c);
   if (a.cw_prof || a.prof) {  // the iteration profile: its own instances (SYN = false), or an error
-    if (a.syn || !a.ref_bits || a.iter_count < 1) return hipErrorInvalidValue;
-    if (a.iter_count > kBpProfMaxIter || c.Kw > kIrrProfMaxKw) return hipErrorNotSupported;
+    if (hipError_t e = prof_launch_check(a, c.Kw <= kIrrProfMaxKw)) return e;
     return launch_irr_t<T, false, true>(c, a, s, fast);
   }
   return a.syn ? launch_irr_t<T, true>(c, a, s, fast) : launch_irr_t<T, false>(c, a, s, fast);

@@ -44,6 +44,7 @@
 #include <type_traits>
 
 #include "bp_common.hpp"
+#include "bp_launch.hpp"
 #include "demap_common.hpp"
 #include "kernels.hpp"
 
@@ -686,50 +687,27 @@ __global__ __launch_bounds__(T) void bp_regular_kernel(DevCode c, BpLaunch a, un
 template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT, bool PROF = false>
 hipError_t launch_reg_one(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
   auto kern = bp_regular_kernel<T, RV, RC, DV, DC, SYN, DMB, EXACT, PROF>;
-  const size_t lds = reg_lds_bytes(c.E, c.N, c.K, DMB);
-  hipError_t e;
-  if constexpr (PROF) {  // the profile's static LDS counts against the same limit
-    hipFuncAttributes fa;
-    e = hipFuncGetAttributes(&fa, (const void *)kern);
-    if (e != hipSuccess) return e;
-    if (lds + fa.sharedSizeBytes > 160 * 1024) return hipErrorNotSupported;
-  }
-  e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  long long grid = ncu;
-  if (grid > a.B) grid = a.B;
-  e = hipMemsetAsync(a.queue, 0, sizeof(unsigned int), s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T), lds, s, c, a, a.queue, fast_allowed);
-  return hipGetLastError();
+  return launch_persistent(kern, T, reg_lds_bytes(c.E, c.N, c.K, DMB), 1, kNoGridCap, PROF, a, s, c, a, a.queue,
+                           fast_allowed);
 }
 
-// The FAST kernel over the batch, then the exact kernel over the codewords it
-// deferred (usually none: its workgroups read a zero count and leave); with
-// FAST division off, the exact kernel over the batch.
+// FAST kernel, then the exact kernel over its defer list; with FAST division
+// off, the exact kernel over the batch.
 template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool PROF = false>
 hipError_t launch_reg_t(const DevCode &c, const BpLaunch &a, hipStream_t s, int fast_allowed) {
   const size_t lds = reg_lds_bytes(c.E, c.N, c.K, DMB);
-  if (lds > 160 * 1024 || c.K > 65536 || c.N > 65536 || c.Kw > kRegMaxKw) return hipErrorNotSupported;
+  if (lds > kLdsLimit || c.K > 65536 || c.N > 65536 || c.Kw > kRegMaxKw) return hipErrorNotSupported;
   if (!(fast_allowed & 1)) return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true, PROF>(c, a, s, 0);
-  if (!a.defer_idx || !a.defer_cnt) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(a.defer_cnt, 0, sizeof(unsigned), s);
-  if (e != hipSuccess) return e;
-  e = launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, false, PROF>(c, a, s, fast_allowed);
-  if (e != hipSuccess) return e;
-  BpLaunch b = a;
-  b.cw_idx = a.defer_idx;
-  b.B_dev = a.defer_cnt;
-  return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true, PROF>(c, b, s, 0);
+  return launch_fast_then_exact(
+      a, s,
+      [&](const BpLaunch &b) { return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, false, PROF>(c, b, s, fast_allowed); },
+      [&](const BpLaunch &b) { return launch_reg_one<T, RV, RC, DV, DC, SYN, DMB, true, PROF>(c, b, s, 0); });
 }
 
 }  // namespace
 
 int bp_regular_threads(int N, int M, int E, int dv_max, int dc_max, int regular) {
-  if (!regular || (long long)E * 16 + kRedBytes + N > 160 * 1024) return 0;
+  if (!regular || (size_t)E * 16 + kRedBytes + (size_t)N > kLdsLimit) return 0;
   // PEG2304-class: dv 3, dc 6, N = 3*768, 2M = 3*768
   if (dv_max == 3 && dc_max == 6 && N == 3 * 768 && 2 * M == 3 * 768) return 768;
   return 0;
@@ -740,8 +718,7 @@ hipError_t launch_bp_regular(const DevCode &c, const BpLaunch &a, hipStream_t s)
     return hipErrorNotSupported;
   const int fast = bp_fast_mode(c);
   if (a.cw_prof || a.prof) {  // the iteration profile: its own instances (SYN = false), or an error
-    if (a.syn || !a.ref_bits || a.iter_count < 1) return hipErrorInvalidValue;
-    if (a.iter_count > kBpProfMaxIter) return hipErrorNotSupported;
+    if (hipError_t e = prof_launch_check(a)) return e;
     if (a.sym_y) {
       if (!bp_regular_fuses_demap(c, a.sym_bits) || a.cw_idx || a.p0_sel) return hipErrorNotSupported;
       return launch_reg_t<768, 3, 3, 3, 6, false, 2, true>(c, a, s, fast);
@@ -777,7 +754,7 @@ bool bp_regular_fuses_demap(const DevCode &c, int bits) {
   if (const char *e = getenv("KML_FUSED_DEMAP"))
     if (e[0] == '0') return false;
   return c.reg_c2v && bp_regular_threads(c.N, c.M, c.E, c.dv_max, c.dc_max, c.regular) == 768 && c.punct == 0 &&
-         bits == 2 && c.cc_len % bits == 0 && reg_lds_bytes(c.E, c.N, c.K, 2) <= 160 * 1024;
+         bits == 2 && c.cc_len % bits == 0 && reg_lds_bytes(c.E, c.N, c.K, 2) <= kLdsLimit;
 }
 
 }  // namespace kml

@@ -38,6 +38,7 @@
 #include <cstdlib>
 
 #include "bp_common.hpp"
+#include "bp_launch.hpp"
 #include "demap_common.hpp"
 #include "kernels.hpp"
 
@@ -399,38 +400,21 @@ __global__ __launch_bounds__(T) void bp_regular_f32_kernel(DevCode c, BpLaunch a
 template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB, bool EXACT>
 hipError_t launch_f32_one(const DevCode &c, const BpLaunch &a, hipStream_t s) {
   auto kern = bp_regular_f32_kernel<T, RV, RC, DV, DC, SYN, DMB, EXACT>;
-  const size_t lds = f32_lds_bytes(c.E, c.N, c.K);
-  hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  long long grid = ncu;
-  if (grid > a.B) grid = a.B;
-  e = hipMemsetAsync(a.queue, 0, sizeof(unsigned int), s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T), lds, s, c, a, a.queue);
-  return hipGetLastError();
+  return launch_persistent(kern, T, f32_lds_bytes(c.E, c.N, c.K), 1, kNoGridCap, false, a, s, c, a, a.queue);
 }
 
+// Without the fused demap there is no FAST division and one launch; with it,
+// the FAST-demap launch, then the exact-demap launch over its defer list.
 template <int T, int RV, int RC, int DV, int DC, bool SYN, int DMB>
 hipError_t launch_f32_t(const DevCode &c, const BpLaunch &a, hipStream_t s) {
   const size_t lds = f32_lds_bytes(c.E, c.N, c.K);
-  if (lds > 160 * 1024 || c.N > c.E || c.K > 65536 || c.N > 65536 || c.Kw > kF32MaxKw) return hipErrorNotSupported;
+  if (lds > kLdsLimit || c.N > c.E || c.K > 65536 || c.N > 65536 || c.Kw > kF32MaxKw) return hipErrorNotSupported;
   if constexpr (DMB == 0) {
     return launch_f32_one<T, RV, RC, DV, DC, SYN, 0, true>(c, a, s);
   } else {
-    // the FAST-demap launch over the batch, then the exact-demap launch over
-    // the codewords it deferred (usually none)
-    if (!a.defer_idx || !a.defer_cnt) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(a.defer_cnt, 0, sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
-    e = launch_f32_one<T, RV, RC, DV, DC, SYN, DMB, false>(c, a, s);
-    if (e != hipSuccess) return e;
-    BpLaunch b = a;
-    b.cw_idx = a.defer_idx;
-    b.B_dev = a.defer_cnt;
-    return launch_f32_one<T, RV, RC, DV, DC, SYN, DMB, true>(c, b, s);
+    return launch_fast_then_exact(
+        a, s, [&](const BpLaunch &b) { return launch_f32_one<T, RV, RC, DV, DC, SYN, DMB, false>(c, b, s); },
+        [&](const BpLaunch &b) { return launch_f32_one<T, RV, RC, DV, DC, SYN, DMB, true>(c, b, s); });
   }
 }
 
@@ -438,7 +422,7 @@ hipError_t launch_f32_t(const DevCode &c, const BpLaunch &a, hipStream_t s) {
 
 bool bp_regular_f32_supported(const DevCode &c) {
   return c.reg_c2v && c.reg_pos && bp_regular_threads(c.N, c.M, c.E, c.dv_max, c.dc_max, c.regular) == 768 &&
-         f32_lds_bytes(c.E, c.N, c.K) <= 160 * 1024 && c.N <= c.E && c.Kw <= kF32MaxKw;
+         f32_lds_bytes(c.E, c.N, c.K) <= kLdsLimit && c.N <= c.E && c.Kw <= kF32MaxKw;
 }
 
 hipError_t launch_bp_regular_f32(const DevCode &c, const BpLaunch &a, hipStream_t s) {

@@ -162,24 +162,37 @@ int hip_fail(kml_ctx *c, hipError_t e, const char *what) {
     if (_e != hipSuccess) return hip_fail(ctx, _e, what); \
   } while (0)
 
+// Packs the graph's arrays into one device allocation: add() each array,
+// copy `host` to the device once, then ptr() each handle.
+struct GraphPacker {
+  std::vector<unsigned char> host;
+  const unsigned char *base = nullptr;  // the device copy, set after the upload
+  template <class T>
+  size_t add(const std::vector<T> &v, size_t min_elems = 0) {
+    const size_t off = (host.size() + 255) & ~size_t(255);
+    host.resize(off + std::max(v.size(), min_elems) * sizeof(T), 0);
+    if (!v.empty()) memcpy(host.data() + off, v.data(), v.size() * sizeof(T));
+    return off;
+  }
+  template <class T>
+  const T *ptr(size_t handle) const {
+    return reinterpret_cast<const T *>(base + handle);
+  }
+};
+
 int upload_code(kml_ctx *c) {
   const kml::LdpcCode &L = c->code;
-  // pack all int32 arrays + enc words into one allocation
-  std::vector<size_t> off;
-  size_t bytes = 0;
-  auto reserve = [&](size_t n) {
-    bytes = (bytes + 255) & ~size_t(255);
-    off.push_back(bytes);
-    bytes += n;
-  };
-  reserve(L.row_ptr.size() * 4);
-  reserve(L.row_col.size() * 4);
-  reserve(L.col_ptr.size() * 4);
-  int regular = 1;
-  for (int j = 0; j < L.N; j++)
-    if (L.col_ptr[j + 1] - L.col_ptr[j] != L.dv_max) regular = 0;
-  for (int i = 0; i < L.M; i++)
-    if (L.row_ptr[i + 1] - L.row_ptr[i] != L.dc_max) regular = 0;
+  int regular = 1, irr_ok = 1;
+  for (int j = 0; j < L.N; j++) {
+    const int dv = L.col_ptr[j + 1] - L.col_ptr[j];
+    if (dv != L.dv_max) regular = 0;
+    if (dv < 1 || dv > 9) irr_ok = 0;
+  }
+  for (int i = 0; i < L.M; i++) {
+    const int dc = L.row_ptr[i + 1] - L.row_ptr[i];
+    if (dc != L.dc_max) regular = 0;
+    if (dc < 2 || dc > 10) irr_ok = 0;
+  }
   const int reg_T = kml::bp_regular_threads(L.N, L.M, L.E, L.dv_max, L.dc_max, regular);
   kml::RegularLayout plan;
   if (reg_T > 0) kml::plan_regular_layout(L, reg_T, plan);
@@ -188,12 +201,6 @@ int upload_code(kml_ctx *c) {
     plan.pos.assign(L.N, 0);
     for (int p = 0; p < L.N; p++) plan.pos[L.vn_order[p]] = p;
   }
-  reserve(L.col_slot.size() * 4);
-  reserve(vn_order.size() * 4);
-  reserve(L.cn_order.size() * 4);
-  reserve(std::max<size_t>(L.enc_info.size(), 1) * 8);
-  reserve(plan.c2v_addr.size() * 4);
-  reserve(plan.pos.size() * 4);
   // partition plan of the partitioned cooperative kernel (codes whose slots exceed one CU's LDS)
   kml::PartitionPlan part;
   const int part_G = kml::bp_part_group_size(L.N, L.M, L.E, L.dv_max, L.dc_max, regular);
@@ -205,79 +212,51 @@ int upload_code(kml_ctx *c) {
   for (int m = 0; part.G && m < part.G; m++)
     part_xmax = std::max({part_xmax, part.xr_ptr[m + 1] - part.xr_ptr[m], part.xc_ptr[m + 1] - part.xc_ptr[m]});
   if (part.G && !kml::part_plan_fits(part.G, L.N, L.M, L.E, part.ncut, part.mirror_max, part_xmax)) part.G = 0;
-  reserve(part.vn.size() * 4);
-  reserve(part.cn.size() * 4);
-  reserve(part.pos.size() * 4);
-  reserve(part.vaddr.size() * 4);
-  reserve(part.xr.size() * 4);
-  reserve(part.xr_ptr.size() * 4);
-  reserve(part.xc.size() * 4);
-  reserve(part.xc_ptr.size() * 4);
-  reserve(part.vx.size() * 4);
-  reserve(part.rx.size() * 4);
   // round plan of the irregular-code kernel (layout.hpp IrregularPlan)
   kml::IrregularPlan irr;
   if (!regular && !kml::plan_irregular(L, kml::kIrrThreads, kml::kIrrVnPairMax, kml::kIrrCnPairMax, irr))
     irr = kml::IrregularPlan();
-  reserve(irr.vn.size() * 4);
-  reserve(irr.cn.size() * 4);
-  reserve(irr.cn_base.size() * 4);
-  reserve(irr.col_slot.size() * 4);
-  HIPCHK(c, c->d_graph.ensure(bytes), "hipMalloc(graph)");
-  std::vector<unsigned char> host(bytes, 0);
-  auto put = [&](int i, const void *src, size_t n) {
-    if (n) memcpy(host.data() + off[i], src, n);
-  };
-  put(0, L.row_ptr.data(), L.row_ptr.size() * 4);
-  put(1, L.row_col.data(), L.row_col.size() * 4);
-  put(2, L.col_ptr.data(), L.col_ptr.size() * 4);
-  put(3, L.col_slot.data(), L.col_slot.size() * 4);
-  put(4, vn_order.data(), vn_order.size() * 4);
-  put(5, L.cn_order.data(), L.cn_order.size() * 4);
-  put(6, L.enc_info.data(), L.enc_info.size() * 8);
-  put(7, plan.c2v_addr.data(), plan.c2v_addr.size() * 4);
-  put(8, plan.pos.data(), plan.pos.size() * 4);
-  put(9, part.vn.data(), part.vn.size() * 4);
-  put(10, part.cn.data(), part.cn.size() * 4);
-  put(11, part.pos.data(), part.pos.size() * 4);
-  put(12, part.vaddr.data(), part.vaddr.size() * 4);
-  put(13, part.xr.data(), part.xr.size() * 4);
-  put(14, part.xr_ptr.data(), part.xr_ptr.size() * 4);
-  put(15, part.xc.data(), part.xc.size() * 4);
-  put(16, part.xc_ptr.data(), part.xc_ptr.size() * 4);
-  put(17, part.vx.data(), part.vx.size() * 4);
-  put(18, part.rx.data(), part.rx.size() * 4);
-  put(19, irr.vn.data(), irr.vn.size() * 4);
-  put(20, irr.cn.data(), irr.cn.size() * 4);
-  put(21, irr.cn_base.data(), irr.cn_base.size() * 4);
-  put(22, irr.col_slot.data(), irr.col_slot.size() * 4);
-  HIPCHK(c, hipMemcpy(c->d_graph.p, host.data(), bytes, hipMemcpyHostToDevice), "upload graph");
-  unsigned char *base = c->d_graph.as<unsigned char>();
+
+  // all int32 arrays + the encoder words in one allocation
+  GraphPacker g;
+  const size_t row_ptr = g.add(L.row_ptr), row_col = g.add(L.row_col), col_ptr = g.add(L.col_ptr);
+  const size_t col_slot = g.add(L.col_slot), vn_ord = g.add(vn_order), cn_ord = g.add(L.cn_order);
+  const size_t enc_info = g.add(L.enc_info, 1);
+  const size_t reg_c2v = g.add(plan.c2v_addr), reg_pos = g.add(plan.pos);
+  const size_t pt_vn = g.add(part.vn), pt_cn = g.add(part.cn), pt_pos = g.add(part.pos), pt_vaddr = g.add(part.vaddr);
+  const size_t pt_xr = g.add(part.xr), pt_xr_ptr = g.add(part.xr_ptr), pt_xc = g.add(part.xc);
+  const size_t pt_xc_ptr = g.add(part.xc_ptr), pt_vx = g.add(part.vx), pt_rx = g.add(part.rx);
+  const size_t irr_vn = g.add(irr.vn), irr_cn = g.add(irr.cn), irr_cn_base = g.add(irr.cn_base);
+  const size_t irr_col_slot = g.add(irr.col_slot);
+  HIPCHK(c, c->d_graph.ensure(g.host.size()), "hipMalloc(graph)");
+  HIPCHK(c, hipMemcpy(c->d_graph.p, g.host.data(), g.host.size(), hipMemcpyHostToDevice), "upload graph");
+  g.base = c->d_graph.as<unsigned char>();
+  auto i32 = [&](size_t handle, bool present = true) { return present ? g.ptr<int32_t>(handle) : nullptr; };
   kml::DevCode &d = c->dc;
-  d.row_ptr = reinterpret_cast<const int32_t *>(base + off[0]);
-  d.row_col = reinterpret_cast<const int32_t *>(base + off[1]);
-  d.col_ptr = reinterpret_cast<const int32_t *>(base + off[2]);
-  d.col_slot = reinterpret_cast<const int32_t *>(base + off[3]);
-  d.vn_order = reinterpret_cast<const int32_t *>(base + off[4]);
-  d.cn_order = reinterpret_cast<const int32_t *>(base + off[5]);
-  d.enc_info = reinterpret_cast<const uint64_t *>(base + off[6]);
-  d.reg_c2v = reg_T > 0 ? reinterpret_cast<const int32_t *>(base + off[7]) : nullptr;
-  d.reg_pos = reinterpret_cast<const int32_t *>(base + off[8]);
+  d.row_ptr = i32(row_ptr);
+  d.row_col = i32(row_col);
+  d.col_ptr = i32(col_ptr);
+  d.col_slot = i32(col_slot);
+  d.vn_order = i32(vn_ord);
+  d.cn_order = i32(cn_ord);
+  d.enc_info = g.ptr<uint64_t>(enc_info);
+  d.reg_c2v = i32(reg_c2v, reg_T > 0);
+  d.reg_pos = i32(reg_pos);
   d.pt_G = part.G;
-  d.pt_vn = part.G ? reinterpret_cast<const int32_t *>(base + off[9]) : nullptr;
-  d.pt_cn = part.G ? reinterpret_cast<const int32_t *>(base + off[10]) : nullptr;
-  d.pt_pos = part.G ? reinterpret_cast<const int32_t *>(base + off[11]) : nullptr;
-  d.pt_vaddr = part.G ? reinterpret_cast<const int32_t *>(base + off[12]) : nullptr;
-  d.pt_xr = part.G ? reinterpret_cast<const int32_t *>(base + off[13]) : nullptr;
-  d.pt_xr_ptr = part.G ? reinterpret_cast<const int32_t *>(base + off[14]) : nullptr;
-  d.pt_xc = part.G ? reinterpret_cast<const int32_t *>(base + off[15]) : nullptr;
-  d.pt_xc_ptr = part.G ? reinterpret_cast<const int32_t *>(base + off[16]) : nullptr;
-  d.pt_vx = part.G ? reinterpret_cast<const int32_t *>(base + off[17]) : nullptr;
-  d.pt_rx = part.G ? reinterpret_cast<const int32_t *>(base + off[18]) : nullptr;
-  d.irr_vn = irr.vn.empty() ? nullptr : reinterpret_cast<const int32_t *>(base + off[19]);
-  d.irr_cn = irr.cn.empty() ? nullptr : reinterpret_cast<const int32_t *>(base + off[20]);
-  d.irr_cn_base = irr.cn.empty() ? nullptr : reinterpret_cast<const int32_t *>(base + off[21]);
-  d.irr_col_slot = irr.cn.empty() ? nullptr : reinterpret_cast<const int32_t *>(base + off[22]);
+  d.pt_vn = i32(pt_vn, part.G);
+  d.pt_cn = i32(pt_cn, part.G);
+  d.pt_pos = i32(pt_pos, part.G);
+  d.pt_vaddr = i32(pt_vaddr, part.G);
+  d.pt_xr = i32(pt_xr, part.G);
+  d.pt_xr_ptr = i32(pt_xr_ptr, part.G);
+  d.pt_xc = i32(pt_xc, part.G);
+  d.pt_xc_ptr = i32(pt_xc_ptr, part.G);
+  d.pt_vx = i32(pt_vx, part.G);
+  d.pt_rx = i32(pt_rx, part.G);
+  d.irr_vn = i32(irr_vn, !irr.vn.empty());
+  d.irr_cn = i32(irr_cn, !irr.cn.empty());
+  d.irr_cn_base = i32(irr_cn_base, !irr.cn.empty());
+  d.irr_col_slot = i32(irr_col_slot, !irr.cn.empty());
   d.irr_slots = irr.n_slots;
   d.pt_ncut = part.ncut;
   d.pt_mirror = part.mirror_max;
@@ -301,15 +280,7 @@ int upload_code(kml_ctx *c) {
   d.is5g = L.is5g ? 1 : 0;
   d.active = L.active ? 1 : 0;
   d.regular = regular;
-  d.irr_ok = 1;
-  for (int j = 0; j < L.N; j++) {
-    const int dv = L.col_ptr[j + 1] - L.col_ptr[j];
-    if (dv < 1 || dv > 9) d.irr_ok = 0;
-  }
-  for (int i = 0; i < L.M; i++) {
-    const int dc = L.row_ptr[i + 1] - L.row_ptr[i];
-    if (dc < 2 || dc > 10) d.irr_ok = 0;
-  }
+  d.irr_ok = irr_ok;
 
   HIPCHK(c, c->d_cons.ensure(sizeof(double) * (c->modem.pts.size() + 8)), "hipMalloc(cons)");
   kml::rotation_factors(c->rot);

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <algorithm>
 
+#include "bp_launch.hpp"  // device_cus
 #include "demap_common.hpp"
 #include "kernels.hpp"
 
@@ -379,9 +380,7 @@ hipError_t launch_demap(int bits, const double *cons, const double2 *y, int S, i
   const long long n = (long long)B * S;
   if (n == 0) return hipSuccess;
   if (n > 0x7FFFFFFFLL || !d.idx || !d.cnt || d.cap < 1) return hipErrorInvalidValue;  // int32 symbol indices
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int ncu = device_cus();
   // small constellations: 8 workgroups per CU, grid-stride; 64QAM (long
   // symbols): one symbol per thread
   const long long wg = (n + 255) / 256;
@@ -426,9 +425,7 @@ hipError_t launch_cand_metric(const DevCode &c, int bits, const double *cons, co
   if (nc < 1 || nc > 4) return hipErrorInvalidValue;
   if (!d.idx || !d.cnt || d.cap < B) return hipErrorInvalidValue;  // every codeword may defer
   const size_t lds = 32 + ((4 * (size_t)c.cc_len + 3) & ~(size_t)3) + (bits >= 5 ? 4 * (size_t)kRescanCap : 0);
-  int dev = 0, ncu = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int ncu = device_cus();
   const dim3 grid(B), xgrid((unsigned)std::min(B, 2 * ncu)), blk(256);
   // KML_CM_NOSCREEN=1 (tests): a NaN 1 / var fails every screen (hard_bits_screen
   // returns false), so every (candidate, symbol) takes the demapper
