@@ -85,7 +85,7 @@ struct BpLaunch {
   long long gslots_cap = 0;      // number of double2 available
   unsigned int *queue = nullptr; // 4-byte device dequeue counter (zeroed by the launcher)
   // Cooperative kernels: clear the abort word before the launch.  The caller
-  // clears it only for the first launch after the last check (capi.cpp sync),
+  // clears it only for the first launch after the last check (context.cpp sync),
   // so a timeout in an earlier launch of the same API call stays visible.
   bool reset_abort = true;
   // Fused demap (bp_regular.hip only, bp_regular_fuses_demap): when sym_y is

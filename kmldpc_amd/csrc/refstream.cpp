@@ -98,7 +98,7 @@ void kml_get_sym_str(int64_t *state, int32_t *uu, int qary, int len) {
 
 }  // extern "C"
 
-// needs the context internals (code + modem): defined in capi.cpp through this hook
+// needs the context internals (code + modem): capi.cpp's kml_ref_frames calls this hook
 namespace kml {
 int ref_frames(const LdpcCode &code, const Modem &modem, int64_t *state, double snr, int n, uint8_t *uu_out,
                double *h_out, double *y_out) {

@@ -2,7 +2,8 @@
 // (tests/test_host.py::test_host_code_under_sanitizers): the planner, the config
 // parser, the constellation loader and the reference-stream frame generator run
 // on the reference's data files AND on malformed inputs (truncated / garbage
-// files, broken TOML), so every error path is walked with the sanitizers on.
+// files, broken TOML), so every error path is walked with the sanitizers on;
+// and the MAT-file writer writes one small file.
 // Prints "san_errors=0" on success (the sanitizers themselves abort on a finding).
 //   host_san_check <data dir> <scratch dir>
 #include <cstdio>
@@ -12,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/kmldpc_amd.h"
 #include "code.hpp"
 #include "config.hpp"
 #include "layout.hpp"
@@ -158,6 +160,24 @@ static void check_config(const std::string &scratch, const std::string &data) {
   CHECK(!load_run_config(scratch + "/bad.toml", data, rc, err), "bad run config accepted");
 }
 
+// kml_kmeans_dump_mat (matfile.cpp) for S = 5, Kc = 4: the 128-byte header and
+// six uncompressed variables, each tag + flags + dims + name + data padded to 8
+// bytes: data 152, cluster 136, idx 88, constellations 144, hHats 136, realH 88.
+static void check_mat(const std::string &scratch) {
+  const int S = 5, Kc = 4;
+  double data[2 * S], clusters[2 * Kc], cons[2 * Kc], append[10];
+  int32_t idx[S];
+  for (int i = 0; i < 2 * S; i++) data[i] = 0.25 * i;
+  for (int i = 0; i < 2 * Kc; i++) clusters[i] = -1.0 * i, cons[i] = 0.5 * i;
+  for (int i = 0; i < 10; i++) append[i] = 1.0 + i;
+  for (int i = 0; i < S; i++) idx[i] = i % Kc;
+  const std::string path = scratch + "/km.mat";
+  CHECK(kml_kmeans_dump_mat(path.c_str(), data, S, clusters, idx, cons, Kc, append) == KML_OK, "dump failed");
+  CHECK(slurp(path).size() == 872, "MAT file of " + std::to_string(slurp(path).size()) + " bytes, expected 872");
+  CHECK(kml_kmeans_dump_mat((scratch + "/no/such/dir.mat").c_str(), data, S, clusters, idx, cons, Kc, append) ==
+            KML_E_IO, "unwritable path accepted");
+}
+
 int main(int argc, char **argv) {
   if (argc < 3) {
     printf("usage: host_san_check <data dir> <scratch dir>\n");
@@ -185,6 +205,7 @@ int main(int argc, char **argv) {
     check_code(scratch + "/" + codes[k], k == 1, *cm[k], -1 - k);
   }
   check_config(scratch, data);
+  check_mat(scratch);
   printf("san_errors=%d\n", errors);
   return errors != 0;
 }

@@ -250,7 +250,7 @@ def test_kernel_placement_plans(tmp_path, data_dir):
 
 def test_host_code_under_sanitizers(tmp_path, data_dir):
     """The host side of the library (planner, GF(2) elimination + encoder,
-    TOML reader, constellation loader, reference frame stream) built with
+    TOML reader, constellation loader, reference frame stream, MAT writer) built with
     AddressSanitizer + UndefinedBehaviorSanitizer: the placement-plan checks on
     the reference's H files, encoded codewords with a zero syndrome, and the
     error paths on truncated / garbage H and constellation files and broken
@@ -262,7 +262,8 @@ def test_host_code_under_sanitizers(tmp_path, data_dir):
     csrc = os.path.join(REPO, "kmldpc_amd", "csrc")
     flags = ["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
              "-fno-omit-frame-pointer", "-I", csrc]
-    host = [os.path.join(csrc, f) for f in ("code.cpp", "layout.cpp", "config.cpp", "modem.cpp", "refstream.cpp")]
+    host = [os.path.join(csrc, f) for f in ("code.cpp", "layout.cpp", "config.cpp", "modem.cpp", "refstream.cpp",
+                                               "matfile.cpp")]
     # the partition refinement's annealing at a short schedule (its full length
     # runs in test_kernel_placement_plans)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
@@ -283,6 +284,24 @@ def test_host_code_under_sanitizers(tmp_path, data_dir):
     assert out.returncode == 0, out.stdout + out.stderr[-4000:]
     assert "plan_errors=0" in out.stdout
     assert out.stdout.count("partition: ") == 2 and out.stdout.count("census syn_irr1200.txt") == 2, out.stdout
+
+
+def test_soft_metric_walk_under_sanitizers(tmp_path):
+    """The soft-syndrome metric's host walk (kmldpc_amd/csrc/soft_walk.hpp: the
+    stale syndrom_soft_ reads resolved in codeword order, final decodes that
+    repeat their metric decode skipped, one round per link that does not)
+    against a naive model that decodes the codewords one by one, on 4000
+    seeded cases (tests/native/soft_walk_check.cpp): chosen, metrics and the
+    final state bit-equal, every codeword listed once, in order and only after
+    its choice is final, no more feed-backs than non-repeating final decodes."""
+    exe = tmp_path / "swc"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I", os.path.join(REPO, "kmldpc_amd", "csrc"), "-o", str(exe),
+                    os.path.join(REPO, "tests", "native", "soft_walk_check.cpp")], check=True)
+    out = subprocess.run([str(exe), "4000"], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
+    assert out.returncode == 0, out.stdout + out.stderr[-4000:]
+    assert "cases=4000 soft_walk_errors=0" in out.stdout
 
 
 def test_cn_division_tail_exact_near_one():
