@@ -700,8 +700,10 @@ __device__ __forceinline__ cplx cdiv_const(cplx n, cplx dd, const CdivConst &k) 
 // the assignment and the rebuilds); a word's membership bits and drift
 // threshold live in the registers of lane = word (S <= 4096); LDS holds the
 // cluster-0 members' VALUES in ascending symbol order (capacity S/3; a larger
-// cluster 0, seen only on degenerate inputs, is summed straight from the
-// words), the cluster points, the constellation and the launch constants
+// cluster 0 is summed straight from the words: with four or more points that
+// happens only on degenerate inputs, with two points (BPSK) cluster 0 holds
+// about S/2 symbols and it is the path of every frame), the cluster points,
+// the constellation and the launch constants
 // (6.3 KB per PEG2304/QPSK codeword).  Residency is set by registers (6 waves
 // per SIMD) and there is no workgroup barrier at all.  The real and the
 // imaginary chains are summed by the same wave one after the other (both in
@@ -1057,7 +1059,7 @@ __global__ __launch_bounds__(64 * kWaveWpg) __attribute__((amdgpu_waves_per_eu(k
     cnt += n;
     const bool fromwords = kSeg ? !listok : n > L.cap;
     const int nscan = kSeg ? nlist : n;
-    if (fromwords) {  // more members than the list holds (degenerate input): straight from the words
+    if (fromwords) {  // more members than the list holds (every BPSK frame; else degenerate input): straight from the words
       double acc = lane == 0 ? sr : si;  // lane 0: real chain, lane 1: imaginary chain, ascending j
       for (int w = 0; w < Sw; ++w) {
         const uint64_t bits = lane_u64(wb, w);

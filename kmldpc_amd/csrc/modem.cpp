@@ -48,7 +48,12 @@ bool Modem::load(const std::string &path, std::string &err) {
     }
     pts[2 * i] = re;
     pts[2 * i + 1] = im;
-    energies += std::pow(std::abs(std::complex<double>(re, im)), 2);
+    // modem.cc:122 pow(abs(s), 2): glibc's cabs is hypot, and pow(x, 2) is x * x.
+    // Spelled out, because std::abs(std::complex) need not be hypot under every
+    // compiler and header set, and a file whose energy is not 1 then loads
+    // points an ulp or two off the reference's.
+    const double m = std::hypot(re, im);
+    energies += m * m;
   }
   energies /= Kc;
   const double s = std::sqrt(energies);

@@ -10,6 +10,7 @@ oracle/_ref/ref_harness, built by ``make -C oracle ref``):
     python tests/golden/make_golden.py --bench         # bench/*.npz (bench workload's reference counters)
     python tests/golden/make_golden.py --bench-cases a,b   # the named BENCH_CASES only
     python tests/golden/make_golden.py --bench-large   # bench/large_oracle.json (oracle, 8 streams)
+    python tests/golden/make_golden.py --kmstate [a,b] # kmstate/*.npz (all, or the named KMSTATE_CASES)
 
 What it writes (all small):
   tests/golden/data/*.txt.gz      the reference's H-matrix and constellation data
@@ -18,7 +19,12 @@ What it writes (all small):
                                   /root/reference.  Data, not source.
                                   (the synthetic H files data/syn_*.txt.gz are our
                                   own, written by tests/golden/make_codes.py; their
-                                  cases, SYN_CASES, read them from there)
+                                  cases, SYN_CASES, read them from there; so are the
+                                  synthetic constellations data/syn_*bit*.txt.gz,
+                                  written by tests/golden/make_cons.py, and their
+                                  cases, CONS_CASES: BPSK, Gray 8PSK and a two-ring
+                                  8-point star on PEG2304, BG2 and the synthetic
+                                  codes, under the same both-kinds rule and size cap)
   tests/golden/<case>.npz         per case, seed 17 (CLCRandNum::SetSeed(-1)):
       * stream  : per-codeword chosen candidate, BP return value, error bits and
                   CRC32s of y / P0 / uu_hat / cc_hat / syndrom_soft
@@ -150,6 +156,44 @@ SYN_CASES = {
 }
 CASES.update(SYN_CASES)
 NVEC_CASE.update({"syn_reg36_4080_16qam_blind": 4, "syn_reg36_4160_qpsk_known": 4})
+
+# The synthetic constellations (tests/golden/make_cons.py, data/syn_*bit*.txt.gz):
+# the 1- and 3-bit instances of the front end (demap_kernel / cand_metric_kernel
+# <1> and <3>, k-means at 2 and 8 clusters).  The same both-kinds rule and size
+# cap as SYN_CASES; each SNR was chosen on the reference's own stream to meet it.
+BPSK, PSK8, STAR8 = "syn_1bit_BPSK.txt", "syn_3bits_8PSK_Gray.txt", "syn_3bits_star8.txt"
+CONS_CASES = {
+    # S = 2304: cluster 0 past the member list on the headline code; the separate
+    # demap in front of bp_regular_kernel (the fused form takes bits = 2 only)
+    "peg2304_bpsk_blind": ("PEG2304regular0.5.txt", BPSK, False, False, 20, 0.5, 100, True),
+    "peg2304_8psk_known": ("PEG2304regular0.5.txt", PSK8, False, True, 20, 5.0, 100, True),  # S = 768
+    "syn_reg36_192_bpsk_blind": ("syn_reg36_192.txt", BPSK, False, False, 20, 0.5, 100, True),  # S = 192: three full words
+    # S = 64: exactly one word.  8PSK has eight-fold symmetry and the receiver
+    # tries four rotations, so about half the blind frames fail at any SNR
+    "syn_reg36_192_8psk_blind": ("syn_reg36_192.txt", PSK8, False, False, 20, 12.0, 100, True),
+    # S = 4080: 64 lane-words, the last partial; S = 4160: the native S > 4096
+    # k-means route in front of bp_part_kernel
+    "syn_reg36_4080_bpsk_blind": ("syn_reg36_4080.txt", BPSK, False, False, 20, 0.5, 24, True),
+    "syn_reg36_4160_bpsk_blind": ("syn_reg36_4160.txt", BPSK, False, False, 20, 0.5, 24, True),
+    "bg2_8psk_blind": ("5GLDPCBG2a3_R12_K960.txt", PSK8, True, False, 50, 8.0, 100, True),  # S = 640, 5G puncturing
+    # star8, unequal moduli through k-means, the metric screen and the demapper:
+    # S = 768, and S = 400 (a partial last word) in front of the irregular kernel.
+    # Blind, NO SNR meets the both-kinds rule: KMeans::Run scales its clusters by
+    # (largest symbol) / (point 0), and point 0 lies on the inner ring, so cluster 0
+    # settles on an outer-ring point; h_hat comes out 45 degrees off and 1.4 to 1.8
+    # times too long at every SNR from -3 to 40 dB and no codeword ever stops early
+    # (ONE_KIND below).  The blind cases still pin k-means, the metrics, the chosen
+    # candidate and the max_iter decodes; the known-channel cases at the same SNR
+    # meet the rule and hold the early-stopping star8 codewords.
+    "peg2304_star8_blind": ("PEG2304regular0.5.txt", STAR8, False, False, 20, 8.0, 100, True),
+    "peg2304_star8_known": ("PEG2304regular0.5.txt", STAR8, False, True, 20, 8.0, 100, True),
+    "syn_irr1200_star8_blind": ("syn_irr1200.txt", STAR8, False, False, 20, 8.0, 60, True),
+    "syn_irr1200_star8_known": ("syn_irr1200.txt", STAR8, False, True, 20, 8.0, 60, True),
+}
+CASES.update(CONS_CASES)
+NVEC_CASE.update({"syn_reg36_4080_bpsk_blind": 4, "syn_reg36_4160_bpsk_blind": 4})
+RULED_CASES = {**SYN_CASES, **CONS_CASES}  # checked by check_both_kinds and against MAX_NPZ
+ONE_KIND = ("peg2304_star8_blind", "syn_irr1200_star8_blind")  # every codeword runs to max_iter (see above)
 MAX_NPZ = 926645  # no new fixture is larger than the largest committed before the synthetic codes
 
 COUNTER_CASES = {
@@ -159,8 +203,8 @@ COUNTER_CASES = {
 
 
 def matrix_path(tmp, matrix):
-    """The reference's config/ file, or (the synthetic codes) the repo's own
-    tests/golden/data/<matrix>.gz unpacked into tmp."""
+    """The reference's config/ file, or (the synthetic codes and constellations)
+    the repo's own tests/golden/data/<matrix>.gz unpacked into tmp."""
     ref = os.path.join(REF_CFG, matrix)
     if os.path.exists(ref):
         return ref
@@ -310,15 +354,21 @@ KMSTATE_CASES = {
     "peg2304_qpsk_sm1": ("PEG2304regular0.5.txt", "2bits_QPSK.txt", -1.0, 8),
     "peg2304_16qam_s5": ("PEG2304regular0.5.txt", "4bit_16QAM_Gray.txt", 5.01, 8),
     "peg8064_64qam_s677": ("PEG8064regular0.5.txt", "6bits_64QAM_Gray.txt", 6.77, 4),
+    # the synthetic constellations: 2 clusters (cluster 0 holds about S/2) and 8
+    "peg2304_bpsk_s0": ("PEG2304regular0.5.txt", BPSK, 0.5, 8),
+    "peg2304_star8_s6": ("PEG2304regular0.5.txt", STAR8, 6.0, 8),
 }
 
 
 def make_kmstate(tmp):
     """ref_harness mode kmstate -> golden/kmstate/<name>.npz (y, true_h, clusters, idx)."""
     os.makedirs(os.path.join(HERE, "kmstate"), exist_ok=True)
-    for name, (mat, mod, snr, n) in KMSTATE_CASES.items():
+    arg = sys.argv[sys.argv.index("--kmstate") + 1:]
+    names = arg[0].split(",") if arg else list(KMSTATE_CASES)
+    for name in names:
+        mat, mod, snr, n = KMSTATE_CASES[name]
         cfg = os.path.join(tmp, name + ".toml")
-        write_toml(cfg, REF_CFG, mat, mod, False, False, 20, True)
+        write_toml(cfg, REF_CFG, matrix_path(tmp, mat), matrix_path(tmp, mod), False, False, 20, True)
         out = os.path.join(tmp, name + ".bin")
         subprocess.run([HARNESS, cfg, repr(snr), str(n), out, "kmstate"], check=True)
         buf = open(out, "rb").read()
@@ -421,18 +471,20 @@ def make_frames_cases(tmp, names, check_only=False):
     def one(name):
         mat, mod, is5g, known, it, snr, n, active = CASES[name]
         cfg = os.path.join(tmp, name + ".toml")
-        write_toml(cfg, REF_CFG, matrix_path(tmp, mat), mod, is5g, known, it, active)
+        write_toml(cfg, REF_CFG, matrix_path(tmp, mat), matrix_path(tmp, mod), is5g, known, it, active)
         out = os.path.join(tmp, name + ".bin")
         subprocess.run([HARNESS, cfg, repr(snr), str(n), out], check=True)
         hdr, cons, recs = parse_frames(open(out, "rb").read())
         check_direct(name, recs)
-        if name in SYN_CASES:
+        if name in ONE_KIND:
+            assert all(d["ret"] == it for d in recs), f"{name}: a codeword stops early; move it under the both-kinds rule"
+        elif name in RULED_CASES:
             check_both_kinds(name, recs, it, min(NVEC_CASE.get(name, NVEC), len(recs)))
         if check_only:
             return f"{name}: n={n} KmCodec::Decoder == direct BinaryLDPCCodec::Decoder on every codeword"
         arrs = frames_arrays(hdr, cons, recs, mat, mod, active, min(NVEC_CASE.get(name, NVEC), len(recs)))
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrs)
-        assert name not in SYN_CASES or os.path.getsize(os.path.join(HERE, name + ".npz")) <= MAX_NPZ, name
+        assert name not in RULED_CASES or os.path.getsize(os.path.join(HERE, name + ".npz")) <= MAX_NPZ, name
         return f"{name}: n={n} FER={np.mean(arrs['s_errs'] > 0):.4f} mean_ret={arrs['s_ret'].mean():.2f}"
 
     with ThreadPoolExecutor(4) as ex:

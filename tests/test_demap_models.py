@@ -17,7 +17,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "tools", "probe"))
 
 
-@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"])
+@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt",
+                                   "syn_1bit_BPSK.txt", "syn_3bits_8PSK_Gray.txt", "syn_3bits_star8.txt"])
 def test_metric_screen_never_contradicts_the_oracle(data_dir, modem):
     import screen_model as SM
     from oracle import oracle as O
@@ -42,10 +43,12 @@ def test_metric_screen_never_contradicts_the_oracle(data_dir, modem):
             bits, ok = SM.screen(pts, y, h, var)
             assert np.array_equal(bits[ok], ref[ok])
             decided += int(ok.sum())
-    assert decided > 0.95 * 4800  # the screen decides nearly every symbol
+    # the screen decides nearly every symbol; with two points the quarter-turned
+    # frames (half of them) lie along the decision boundary, where it must defer
+    assert decided > (0.95 if MB > 1 else 0.5) * 4800
 
 
-@pytest.mark.parametrize("MB", [2, 4, 6])
+@pytest.mark.parametrize("MB", [1, 2, 3, 4, 6])
 def test_unweighted_sum_gives_the_same_quotients(MB):
     rng = np.random.default_rng(MB)
     w = 0.5 ** MB

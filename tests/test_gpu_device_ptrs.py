@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 NCW = 3
 FILL = 0xA5
-CONFIGS = ["peg2304_qpsk", "bg2_16qam"]
+CONFIGS = ["peg2304_qpsk", "bg2_16qam", "peg2304_star8"]  # star8: a synthetic 3-bit constellation (make_cons.py)
 H2D, D2H = 1, 2  # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
 
 

@@ -61,6 +61,9 @@ IRR_64 = ("syn_irr1200.txt", "6bits_64QAM_Gray.txt", False)
 REG192 = ("syn_reg36_192.txt", "2bits_QPSK.txt", False)
 REG240 = ("syn_reg48_240.txt", "4bit_16QAM_Gray.txt", False)
 HIGH120 = ("syn_high120.txt", "2bits_QPSK.txt", False)
+# the synthetic constellations (tests/golden/make_cons.py): bits = 1 and 3 in channel_kernel
+REG192_BPSK = ("syn_reg36_192.txt", "syn_1bit_BPSK.txt", False)
+HIGH120_8PSK = ("syn_high120.txt", "syn_3bits_8PSK_Gray.txt", False)  # S = 40
 
 SEED_HI = 0xDEADBEEF00000011  # both key words in use
 SEED_HI1 = 0x0000000100000011  # differs from 0x11 in the high key word only
@@ -125,7 +128,7 @@ def test_high_counter_and_key_words_reach_the_frames(data_dir, code):
 
 # ---- b. h and y
 
-CHANNEL_CASES = [(PEG2304, 4), (BG2, 4), (PEG8064, 4), (REG240, 16), (IRR_64, 8)]
+CHANNEL_CASES = [(PEG2304, 4), (BG2, 4), (PEG8064, 4), (REG240, 16), (IRR_64, 8), (REG192_BPSK, 16), (HIGH120_8PSK, 16)]
 CHANNEL_SEED, CHANNEL_FIRST = SEED_HI, 2**32 + 77
 measured = {"h": 0.0, "y": 0.0}
 
@@ -217,10 +220,10 @@ def test_empty_batch(data_dir):
     assert c["tot_blk"] == 0 and c["tot_bit"] == 0 and c["err_bit"] == 0
 
 
-@pytest.mark.parametrize("code", [IRR_QPSK, HIGH120, REG240], ids=_ids)
+@pytest.mark.parametrize("code", [IRR_QPSK, HIGH120, REG240, REG192_BPSK], ids=_ids)
 def test_load_then_frames_round_trip(data_dir, code):
     """kml_sim_load then kml_sim_frames gives back the frames bit for bit for K off
-    the 64-bit grid (600, 60, 121): the tail word's packing and unpacking agree."""
+    the 64-bit grid (600, 60, 121, 96): the tail word's packing and unpacking agree."""
     ctx = ctx_for(data_dir, code)
     assert ctx.K % 64 != 0
     rng = np.random.default_rng(4)

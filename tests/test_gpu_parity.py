@@ -26,6 +26,17 @@ pytestmark = pytest.mark.gpu
 CASES = case_names()
 _ctx = {}
 
+# The synthetic constellations (tests/golden/make_cons.py): the reference ships
+# 2-, 4- and 6-bit files only; these run the 1- and 3-bit instances
+# (demap_kernel / cand_metric_kernel <1> and <3>, run_kmeans / km_state_kernel
+# <2> and <8>).
+BPSK, PSK8, STAR8 = "syn_1bit_BPSK.txt", "syn_3bits_8PSK_Gray.txt", "syn_3bits_star8.txt"
+MODEMS = ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt", BPSK, PSK8, STAR8]
+# S = 2304 and 768 on PEG2304, S = 64 (exactly one k-means word), S = 400 (a partial last word)
+SYN_CONS_ROWS = [("PEG2304regular0.5.txt", BPSK, 0.5), ("PEG2304regular0.5.txt", PSK8, 5.0),
+                 ("PEG2304regular0.5.txt", STAR8, 8.0), ("syn_reg36_192.txt", PSK8, 8.0),
+                 ("syn_irr1200.txt", STAR8, 8.0)]
+
 
 def crc(a):
     return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
@@ -330,7 +341,7 @@ def test_bp_vs_oracle_stream(data_dir, matrix, modem, is5g, snr, max_iter, n):
     ("PEG8064regular0.5.txt", "4bit_16QAM_Gray.txt", False, 6.0, 40),
     ("5GLDPCBG2a3_R12_K960.txt", "6bits_64QAM_Gray.txt", True, 10.0, 100),
     ("5GLDPCBG2a3_R12_K960.txt", "2bits_QPSK.txt", True, 2.0, 100),
-])
+] + [(mx, md, False, snr, 64) for mx, md, snr in SYN_CONS_ROWS])
 def test_demap_vs_oracle(data_dir, matrix, modem, is5g, snr, n):
     ctx = ctx_for(data_dir, matrix, modem, is5g)
     oc = oracle_for(data_dir, matrix, is5g)
@@ -375,7 +386,7 @@ def _adversarial_symbols(pts, S, B, rng):
     ("PEG2304regular0.5.txt", "4bit_16QAM_Gray.txt", 5.01),
     ("PEG8064regular0.5.txt", "6bits_64QAM_Gray.txt", 6.77),
     ("PEG8064regular0.5.txt", "6bits_64QAM_Gray.txt", 40.0),
-])
+] + SYN_CONS_ROWS)
 def test_demap_and_metric_adversarial(data_dir, matrix, modem, snr):
     """Bit-exact P0 (fast shared-reciprocal divisions with IEEE fallback) and
     bit-exact hard metrics (single-precision screen with exact fallback) on
@@ -437,6 +448,16 @@ def test_fused_demap_matches_separate(data_dir, blind, monkeypatch):
     ("5GLDPCBG2a3_R12_K960.txt", "6bits_64QAM_Gray.txt", True, 11.0, 200),
     ("5GLDPCBG2a3_R12_K960.txt", "4bit_16QAM_phi1.txt", True, 11.0, 100),
     ("5GLDPCBG2a3_R12_K960.txt", "2bits_QPSK.txt", True, 2.0, 200),
+    # the synthetic constellations: S = 64 (exactly one word), 192, 400 (a
+    # partial last word), 2304, 4080 (64 lane-words, the last partial) and 4160
+    # (past kMaxS: "wave" falls back to the two-launch form); with two points
+    # cluster 0 outgrows the member list on every frame
+    ("syn_reg36_192.txt", PSK8, False, 8.0, 64),
+    ("syn_reg36_192.txt", BPSK, False, 0.5, 64),
+    ("syn_irr1200.txt", STAR8, False, 8.0, 64),
+    ("PEG2304regular0.5.txt", BPSK, False, 0.5, 64),
+    ("syn_reg36_4080.txt", BPSK, False, 0.5, 24),
+    ("syn_reg36_4160.txt", BPSK, False, 0.5, 24),
 ])
 @pytest.mark.parametrize("kernel", ["wave", "split"])
 def test_kmeans_vs_oracle(data_dir, matrix, modem, is5g, snr, n, kernel, monkeypatch):
@@ -452,7 +473,7 @@ def test_kmeans_vs_oracle(data_dir, matrix, modem, is5g, snr, n, kernel, monkeyp
         assert np.array_equal(h4[i], O.rotations(ref)), i
 
 
-@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"])
+@pytest.mark.parametrize("modem", MODEMS)
 def test_kmeans_adversarial_ties(data_dir, modem):
     """Symbols exactly on constellation points, on midpoints between points
     (distance ties) and at zero, under exact and rotated channels: the
@@ -485,7 +506,7 @@ def test_kmeans_adversarial_ties(data_dir, modem):
 
 
 @pytest.mark.parametrize("mode", ["wave", "wave_sequential_sum", "wave_every_word", "split"])
-@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"])
+@pytest.mark.parametrize("modem", MODEMS)
 def test_kmeans_cumulative_sum_adversarial(data_dir, modem, mode, monkeypatch):
     """The k-means kernels' cumulative cluster-0 sums (kmeans.hip
     ordered_sum_vals1: binade-segmented grid scans, tie
@@ -938,7 +959,7 @@ def test_kmeans_state_vs_reference(name, data_dir):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"])
+@pytest.mark.parametrize("modem", MODEMS)
 def test_kmeans_cluster0_majority(data_dir, modem):
     """Frames that put more than S/2 symbols into cluster 0, past the member
     list's capacity L.cap = S/3 (km_wave_kernel then sums cluster 0 straight
@@ -973,7 +994,7 @@ def test_kmeans_cluster0_majority(data_dir, modem):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"])
+@pytest.mark.parametrize("modem", MODEMS)
 def test_kmeans_state_adversarial_ties(data_dir, modem):
     """Final assignment with exact distance ties (symbols on midpoints between
     clusters, at zero, on points): idx is the FIRST minimum (min_element)."""
@@ -1139,7 +1160,7 @@ EXACT_MODES = ["KML_NO_FAST", "KML_FORCE_REDO"]
 @pytest.mark.parametrize("mode", EXACT_MODES)
 @pytest.mark.parametrize("case", ["peg2304_qpsk_known", "bg2_16qam_known", "peg8064_64qam_known",
                                   "peg2304_4psk_known_lowsnr", "syn_irr1200_qpsk_known",
-                                  "syn_reg36_4160_qpsk_known"])
+                                  "syn_reg36_4160_qpsk_known", "peg2304_bpsk_blind", "peg2304_8psk_known"])
 def test_exact_path_golden_vectors(case, data_dir, mode, monkeypatch):
     hdr, z = load_case(case)
     monkeypatch.setenv(mode, "1")
@@ -1159,7 +1180,8 @@ def test_exact_path_golden_vectors(case, data_dir, mode, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", EXACT_MODES)
-@pytest.mark.parametrize("case", ["peg2304_qpsk_known", "peg2304_qpsk_blind", "bg2_16qam_blind", "peg8064_64qam_blind"])
+@pytest.mark.parametrize("case", ["peg2304_qpsk_known", "peg2304_qpsk_blind", "bg2_16qam_blind", "peg8064_64qam_blind",
+                                  "peg2304_bpsk_blind", "peg2304_8psk_known"])
 def test_exact_path_reference_stream(case, data_dir, mode, monkeypatch):
     """KmCodec::Decoder on the reference's frames through the exact path and
     through forced redos (fused QPSK demap prologue included): chosen
@@ -1184,7 +1206,7 @@ def test_forced_redo_counts_and_counters(data_dir, monkeypatch):
         assert c1[k] == c0[k], k
 
 
-@pytest.mark.parametrize("modem", ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"])
+@pytest.mark.parametrize("modem", MODEMS)
 def test_candidate_metric_screen_equals_exact_demap(data_dir, modem, monkeypatch):
     """The candidate metric's single-precision screen (demap_common.hpp
     hard_bits_screen: v_exp_f32, fma ordering, fminf, the fmin <= 64 and
@@ -1226,6 +1248,10 @@ def test_candidate_metric_screen_equals_exact_demap(data_dir, modem, monkeypatch
     ("PEG2304regular0.5.txt", "6bits_64QAM_Gray.txt", False, 10.5, 200),
     ("5GLDPCBG2a3_R12_K960.txt", "6bits_64QAM_Gray.txt", True, 11.0, 200),
     ("5GLDPCBG2a3_R12_K960.txt", "2bits_QPSK.txt", True, 2.0, 200),
+    # the synthetic constellations: the separate demap_kernel<1> in front of
+    # bp_regular_kernel, and unequal moduli in front of bp_irregular_kernel
+    ("PEG2304regular0.5.txt", BPSK, False, 0.5, 100),
+    ("syn_irr1200.txt", STAR8, False, 8.0, 64),
 ])
 def test_cross_product_blind_streams_vs_oracle(data_dir, matrix, modem, is5g, snr, n):
     """The (code x constellation) pairs beyond the reference fixtures' 40-100
