@@ -83,7 +83,7 @@ int upload_code(kml_ctx *c) {
   }
   const int reg_T = kml::bp_regular_threads(L.N, L.M, L.E, L.dv_max, L.dc_max, regular);
   kml::RegularLayout plan;
-  if (reg_T > 0) kml::plan_regular_layout(L, reg_T, plan);
+  if (reg_T > 0) kml::plan_regular_layout(L, plan);
   const std::vector<int32_t> &vn_order = reg_T > 0 ? plan.order : L.vn_order;
   if (reg_T <= 0) {  // column -> vn position, used by the cooperative kernel
     plan.pos.assign(L.N, 0);

@@ -1,5 +1,27 @@
-// layout.hpp — LDS placement plan for the regular-code BP kernel (bp_regular.hip).
+// layout.hpp — the host planner: where each BP kernel family's lanes, LDS
+// slots and mailbox entries go.  Three plans, one per family:
+//   RegularLayout  (bp_regular.hip)     which lane owns which column, and the
+//                                       slot half of each c2v message;
+//   PartitionPlan  (bp_coop.hip)        which of G workgroups owns which rows
+//                                       and columns, and the cut-edge exchange;
+//   IrregularPlan  (bp_irregular.hip)   which wave and round runs which
+//                                       columns / rows, and the slot blocks.
+// A plan changes nothing in the arithmetic: any valid plan gives the same
+// decoder output, it only moves work between lanes, so it decides speed (LDS
+// bank conflicts, mailbox traffic, SIMD balance) and nothing else.
 //
+// Every field of the three structs goes into the plan's digest in
+// tests/native/plan_check.cpp, which tests/golden/host/plan_digests.json pins:
+// a field added to a struct must be added to its digest there.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "code.hpp"
+
+namespace kml {
+
+// ------------------------------------------------- RegularLayout (bp_regular)
 // The kernel keeps one 16-byte slot per edge in LDS, in the reference's row
 // traversal order (rows contiguous, so a check-row lane pair reads its row as
 // consecutive slots).  The variable-node phase gathers and scatters those slots
@@ -13,14 +35,6 @@
 //     (`c2v_addr`): rows whose position in the CN phase has bit 2 set store it
 //     in the upper 8 bytes, which makes the CN phase's 16-lane ds_write_b64
 //     groups conflict-free (8 rows x 2 edges on 16 distinct bank pairs).
-#pragma once
-#include <cstdint>
-#include <vector>
-
-#include "code.hpp"
-
-namespace kml {
-
 struct RegularLayout {
   std::vector<int32_t> order;     // position -> column (position = r*T + thread)
   std::vector<int32_t> pos;       // column -> position
@@ -29,13 +43,12 @@ struct RegularLayout {
   long long cost_final = 0;
 };
 
-// T = threads per workgroup of the kernel (positions are grouped by wave).
-void plan_regular_layout(const LdpcCode &L, int T, RegularLayout &out);
+// Positions are grouped by wave (64 consecutive positions) whatever the
+// kernel's workgroup size is, so the plan does not depend on it.  Cached per
+// graph (row_col, col_slot, cn_order).
+void plan_regular_layout(const LdpcCode &L, RegularLayout &out);
 
-}  // namespace kml
-
-namespace kml {
-
+// -------------------------------------------- PartitionPlan (bp_part_kernel)
 // Partition plan for the partitioned cooperative BP kernel (bp_coop.hip,
 // bp_part_kernel): a group of G workgroups decodes one codeword; member m owns
 // the rows [m*MG, (m+1)*MG) and the columns [m*NG, (m+1)*NG) of the orders
@@ -50,8 +63,9 @@ namespace kml {
 // a 6-bit mask); each column owner's share is a few runs.  The planner
 // minimises the number of cut edges (balanced G-way partition of the Tanner
 // graph: alternating majority assignment of columns given rows and rows given
-// columns, capacity-bounded).  Any partition gives the same decoder output: it
-// only moves work between lanes.
+// columns, capacity-bounded, then annealed single-node moves in four seeded
+// chains: layout.cpp PartRefiner).  Any partition gives the same decoder
+// output: it only moves work between lanes.
 struct PartitionPlan {
   int G = 0, MG = 0, NG = 0;
   int ncut = 0;                 // cut edges (mailbox entries)
@@ -75,13 +89,13 @@ struct PartitionPlan {
   bool all_pairs = false;
 };
 
-// False when the code is not regular or M, N are not multiples of G.
+// False when the code is not regular or M, N are not multiples of G.  Reads
+// the refinement's schedule from the environment on every call
+// (KML_PART_REFINE=0: no cut refinement; KML_PART_REFINE_ITERS: annealing
+// steps per chain, default 150 M) and caches per (graph, G, schedule).
 bool plan_partition(const LdpcCode &L, int G, PartitionPlan &out);
 
-}  // namespace kml
-
-namespace kml {
-
+// -------------------------------------------- IrregularPlan (bp_irregular)
 // Round plan of the irregular-code BP kernel (bp_irregular.hip): T threads in
 // W = T/64 waves, three rounds per phase.  In rounds 0 and 1 a lane owns TWO
 // columns (two half-rows) of the same degree and runs their chains

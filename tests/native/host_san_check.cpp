@@ -75,7 +75,7 @@ static void check_code(const std::string &path, bool is5g, const Modem &modem, i
     // plans the kernels use (their own checks are in plan_check.cpp)
     if (L.dv_max == 3 && L.N <= 4096) {
       RegularLayout rl;
-      plan_regular_layout(L, 1024, rl);
+      plan_regular_layout(L, rl);
     }
     if (is5g || L.dv_max != 3) {  // (any non-(3,6) code: whatever it returns, it returns cleanly)
       IrregularPlan ip;

@@ -5,7 +5,13 @@
 // The extra (non-5G) H files are checked in the named role: the irregular
 // plan (with a census line of what its waves hold), the partition plan, or
 // neither plan being made (the code decodes on the generic bp_kernel).
+// After each plan's checks one line pins the plan itself:
+//   digest <regular|irregular|partition> <H file name> <16 hex digits>
+// (tests/golden/host/plan_digests.json holds the recorded lines), and a
+// --partition file is also planned under three refinement schedules in this
+// one process (check_schedules).
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,14 +46,36 @@ static bool load(LdpcCode &L, const char *path, bool is5g) {
   return true;
 }
 
+static const char *base_name(const char *path) { return strrchr(path, '/') ? strrchr(path, '/') + 1 : path; }
+
+// 64-bit FNV-1a over a plan: every array (its elements as int64, then its
+// length) and every scalar (as int64), bytes least significant first.
+struct Digest {
+  uint64_t h = 0xcbf29ce484222325ull;
+  Digest &add(long long v) {
+    for (int b = 0; b < 8; b++) {
+      h ^= ((uint64_t)v >> (8 * b)) & 0xFF;
+      h *= 0x100000001b3ull;
+    }
+    return *this;
+  }
+  Digest &add(const std::vector<int32_t> &a) {
+    for (int32_t x : a) add((long long)x);
+    return add((long long)a.size());
+  }
+  void print(const char *plan, const char *name) const {
+    printf("digest %s %s %016llx\n", plan, name, (unsigned long long)h);
+  }
+};
+
 static int col_deg(const LdpcCode &L, int v) { return L.col_ptr[v + 1] - L.col_ptr[v]; }
 static int row_deg(const LdpcCode &L, int r) { return L.row_ptr[r + 1] - L.row_ptr[r]; }
 
 // bp_regular.hip: rows in CN-position order with the lane pair's edges
 // interleaved; each edge's c2v byte address names its own slot and half.
-static void check_regular(const LdpcCode &L) {
+static void check_regular(const LdpcCode &L, const char *name) {
   RegularLayout P;
-  plan_regular_layout(L, 768, P);
+  plan_regular_layout(L, P);
   CHECK((int)P.order.size() == L.N, "order size %zu", P.order.size());
   std::vector<int> seen(L.N, 0);
   for (int v : P.order) seen[v]++;
@@ -69,6 +97,7 @@ static void check_regular(const LdpcCode &L) {
   }
   CHECK((int)slots.size() == L.E, "distinct slots %zu", slots.size());
   printf("regular: bank-conflict cost %lld -> %lld\n", P.cost_initial, P.cost_final);
+  Digest().add(P.order).add(P.pos).add(P.c2v_addr).add(P.cost_initial).add(P.cost_final).print("regular", name);
 }
 
 static std::string set_str(const std::set<int> &s) {
@@ -111,8 +140,8 @@ static void irregular_census(const LdpcCode &L, const IrregularPlan &P, int T, c
 
 // bp_irregular.hip: three rounds, pairs of equal degree (up to the limits) in
 // rounds 0-1, every column / row exactly once, one degree per paired wave.
-// census: the name to print the census of the plan under.
-static void check_irregular(const LdpcCode &L, const char *census = nullptr) {
+// census: print the census of the plan too.
+static void check_irregular(const LdpcCode &L, const char *name, bool census = false) {
   const int T = kIrrThreads;
   IrregularPlan P;
   CHECK(plan_irregular(L, T, kIrrVnPairMax, kIrrCnPairMax, P), "plan_irregular failed");
@@ -159,12 +188,20 @@ static void check_irregular(const LdpcCode &L, const char *census = nullptr) {
   }
   for (int e = 0; e < L.E; e++) CHECK(P.col_slot[e] == slot_of[L.col_slot[e]], "column edge %d slot", e);
   printf("irregular: plan ok for T=%d, %d slots for %d edges\n", T, P.n_slots, L.E);
-  if (census) irregular_census(L, P, T, census);
+  if (census) irregular_census(L, P, T, name);
+  Digest().add(P.vn).add(P.cn).add(P.cn_base).add(P.col_slot).add(P.n_slots).print("irregular", name);
+}
+
+static Digest digest_partition(const PartitionPlan &P) {
+  Digest d;
+  d.add(P.G).add(P.MG).add(P.NG).add(P.ncut).add(P.mirror_max).add(P.vn).add(P.cn).add(P.pos).add(P.vaddr);
+  d.add(P.xr).add(P.xr_ptr).add(P.xc).add(P.xc_ptr).add(P.vx).add(P.rx).add(P.anneal_initial).add(P.anneal_final);
+  return d.add(P.interior).add(P.all_pairs);
 }
 
 // bp_part_kernel: members own whole column / row blocks; every edge's LDS
 // address of the column side is a row slot of the owner or one of its mirrors.
-static void check_partition(const LdpcCode &L, bool peg8064 = true) {
+static void check_partition(const LdpcCode &L, const char *name, bool peg8064 = true) {
   PartitionPlan P;
   CHECK(plan_partition(L, 4, P), "plan_partition failed");
   if (P.vn.empty()) return;
@@ -222,7 +259,39 @@ static void check_partition(const LdpcCode &L, bool peg8064 = true) {
     xmax = std::max(xmax, std::max(P.xr_ptr[m + 1] - P.xr_ptr[m], P.xc_ptr[m + 1] - P.xc_ptr[m]));
   CHECK(((long long)P.MG * 6 + P.mirror_max + 7) * 16 + L.N <= 160 * 1024, "LDS: mirror_max %d", P.mirror_max);
   CHECK(3LL * P.ncut <= 2LL * L.E && xmax <= 2 * 1024, "cut %d, exchange list %d", P.ncut, xmax);
-  printf("partition: %d of %d edges cut, mirror_max %d\n", P.ncut, L.E, P.mirror_max);
+  printf("partition: %d of %d edges cut, mirror_max %d, interior %d, bank-conflict cost %lld -> %lld\n", P.ncut, L.E,
+         P.mirror_max, P.interior, P.anneal_initial, P.anneal_final);
+  digest_partition(P).print("partition", name);
+}
+
+// The partition plan depends on the refinement's schedule (KML_PART_REFINE,
+// KML_PART_REFINE_ITERS), so the planner's cache is keyed on it: one process
+// asks for the same code under its own schedule, a short one, none, and its own
+// again, and gets each schedule's plan, not the first one made.  Prints
+//   schedules <name>: ncut <own> <3000000 steps> <unrefined>
+static void check_schedules(const LdpcCode &L, const char *name) {
+  const char *vars[2] = {"KML_PART_REFINE", "KML_PART_REFINE_ITERS"};
+  std::string own[2];
+  bool own_set[2];
+  for (int v = 0; v < 2; v++)
+    if ((own_set[v] = getenv(vars[v]) != nullptr)) own[v] = getenv(vars[v]);
+  auto plan_under = [&](const char *refine, const char *iters) {  // nullptr: the process's own value
+    const char *val[2] = {refine, iters};
+    for (int v = 0; v < 2; v++)
+      if (val[v] || own_set[v])
+        setenv(vars[v], val[v] ? val[v] : own[v].c_str(), 1);
+      else
+        unsetenv(vars[v]);
+    PartitionPlan P;
+    CHECK(plan_partition(L, 4, P), "plan_partition failed");
+    return P;
+  };
+  const PartitionPlan a = plan_under(nullptr, nullptr), b = plan_under("1", "3000000"), c = plan_under("0", nullptr),
+                      a2 = plan_under(nullptr, nullptr);
+  CHECK(digest_partition(a2).h == digest_partition(a).h, "%s: the own schedule's plan changed", name);
+  CHECK(digest_partition(b).h != digest_partition(c).h, "%s: refined and unrefined plans equal", name);
+  CHECK(b.ncut < c.ncut, "%s: refined cut %d, unrefined %d", name, b.ncut, c.ncut);
+  printf("schedules %s: ncut %d %d %d\n", name, a.ncut, b.ncut, c.ncut);
 }
 
 // A code that takes neither specialised plan: a regular code gets no irregular
@@ -259,17 +328,18 @@ int main(int argc, char **argv) {
   if (argc < 4) return 2;
   LdpcCode a, b, c;
   if (!load(a, argv[1], false) || !load(b, argv[2], true) || !load(c, argv[3], false)) return 2;
-  check_regular(a);
-  check_irregular(b);
-  check_partition(c);
+  check_regular(a, base_name(argv[1]));
+  check_irregular(b, base_name(argv[2]));
+  check_partition(c, base_name(argv[3]));
   for (int i = 4; i + 1 < argc; i += 2) {
     LdpcCode x;
     if (!load(x, argv[i + 1], false)) return 2;
-    const char *name = strrchr(argv[i + 1], '/') ? strrchr(argv[i + 1], '/') + 1 : argv[i + 1];
+    const char *name = base_name(argv[i + 1]);
     if (!strcmp(argv[i], "--irregular")) {
-      check_irregular(x, name);
+      check_irregular(x, name, true);
     } else if (!strcmp(argv[i], "--partition")) {
-      check_partition(x, false);
+      check_partition(x, name, false);
+      check_schedules(x, name);
     } else if (!strcmp(argv[i], "--none")) {
       check_none(x, name);
     } else {

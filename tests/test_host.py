@@ -40,6 +40,24 @@ def plan_check_args(data_dir):
                                                            for a in (role, os.path.join(data_dir, f))]
 
 
+def plan_digests(stdout):
+    """plan_check's "digest <plan> <H file> <hex>" lines as {plan: {H file: hex}}."""
+    got = {}
+    for m in re.finditer(r"^digest (regular|irregular|partition) (\S+) ([0-9a-f]{16})$", stdout, re.M):
+        assert m[2] not in got.setdefault(m[1], {}), m[0]
+        got[m[1]][m[2]] = m[3]
+    return got
+
+
+def golden_plan_digests(schedule):
+    """The recorded plans (tests/golden/host/plan_digests.json): "full" is the
+    default annealing schedule, "short" KML_PART_REFINE_ITERS=3000000.  To
+    re-record after a deliberate planner change, run plan_check as these tests
+    do at both schedules and copy its digest lines."""
+    with open(os.path.join(REPO, "tests", "golden", "host", "plan_digests.json")) as f:
+        return json.load(f)[schedule]
+
+
 MODEMS = ["2bits_QPSK.txt", "2bits_4PSK.txt", "4bit_16QAM_Gray.txt", "4bit_16QAM_phi1.txt", "4bit_16QAM_phi2.txt",
           "6bits_64QAM_Gray.txt"]
 
@@ -228,6 +246,9 @@ def test_kernel_placement_plans(tmp_path, data_dir):
     out = subprocess.run([str(exe)] + plan_check_args(data_dir), capture_output=True, text=True)
     assert out.returncode == 0, out.stdout
     assert "plan_errors=0" in out.stdout
+    assert plan_digests(out.stdout) == golden_plan_digests("full"), out.stdout  # not only valid plans: THE plans
+    # one process, one code, three schedules (its own, 3 M steps, unrefined): each gets its own plan's cut
+    assert "schedules syn_reg36_4160.txt: ncut 2809 3001 3431\n" in out.stdout, out.stdout
     # syn_irr1200 is built to reach what BG2's plan never does: the census of its plan
     with open(os.path.join(data_dir, "syn_irr1200.txt")) as f:
         rows = [ln.split() for ln in f.read().splitlines()[3:]]
@@ -285,6 +306,8 @@ def test_host_code_under_sanitizers(tmp_path, data_dir):
                          timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr[-4000:]
     assert "plan_errors=0" in out.stdout
+    assert plan_digests(out.stdout) == golden_plan_digests("short"), out.stdout
+    assert "schedules syn_reg36_4160.txt: ncut 3001 3001 3431\n" in out.stdout, out.stdout  # (its own is the short one)
     assert out.stdout.count("partition: ") == 2 and out.stdout.count("census syn_irr1200.txt") == 2, out.stdout
 
 
