@@ -21,6 +21,13 @@ What each code is for (the kernel family it must decode on):
   syn_reg36_4080   (3,6) regular beyond LDS, 4080 / 4 not a multiple of 16:
                    bp_kernel with global slots
   syn_reg36_4160   (3,6) regular, NG = 1040, MG = 520: bp_part_kernel
+  syn_reg36_2304   (3,6) regular, 2304 x 1152, full rank: bp_regular_kernel and
+                   bp_regular_f32_kernel on a graph that is not PEG2304 (26 4-cycles
+                   where PEG2304 has none, its own placement plan and
+                   systematic-form column swaps), K = 1152
+  syn_reg36_2304_r1147  the same class with five pairs of identical rows (rows
+                   that share six columns; 93 4-cycles): rank 1147, K = 1157
+                   (Kw = 19, five bits in the last word), chk = 1147
 """
 import gzip
 import os
@@ -46,7 +53,16 @@ CODES = {
     "syn_high120": (120, {20: 6, 12: 12, 5: 30, 3: 72}, {30: 4, 13: 10, 9: 12, 8: 34}, 60),
     "syn_reg36_4080": (4080, {3: 4080}, {6: 2040}, 2040),
     "syn_reg36_4160": (4160, {3: 4160}, {6: 2080}, 2080),
+    "syn_reg36_2304": (2304, {3: 2304}, {6: 1152}, 1152),
+    "syn_reg36_2304_r1147": (2305, {3: 2304}, {6: 1152}, 1147),
 }
+# Pairs of identical rows.  A code whose columns all have odd degree cannot lose
+# rank the way syn_reg48_240 does (its rows do not sum to zero), so d pairs of
+# equal rows take d off the rank instead: 6 d columns keep one edge for the
+# configuration model over the other M - 2 d rows, each pair then covers six of
+# them twice, and the row order is shuffled.  Two equal rows share six columns
+# and no edge, so the graph stays simple and the degrees are the profiles'.
+TWIN_ROWS = {"syn_reg36_2304_r1147": 5}
 
 
 def configuration_model(rng, col_deg, row_deg):
@@ -102,8 +118,21 @@ def make(name):
     row_deg = expand(rprof)
     col_deg = col_deg[rng.permutation(len(col_deg))]
     row_deg = row_deg[rng.permutation(len(row_deg))]
-    rows, cols = configuration_model(rng, col_deg, row_deg)
     M, N = len(row_deg), len(col_deg)
+    d = TWIN_ROWS.get(name, 0)
+    if d:
+        assert (row_deg[M - 2 * d:] == 6).all()
+        twin_cols = rng.permutation(N)[:6 * d]
+        col_deg[twin_cols] -= 2
+        rows, cols = configuration_model(rng, col_deg, row_deg[:M - 2 * d])
+        col_deg[twin_cols] += 2
+        rows = np.concatenate([rows, M - 2 * d + np.repeat(np.arange(2 * d), 6)])
+        cols = np.concatenate([cols, np.repeat(twin_cols.reshape(d, 6), 2, axis=0).reshape(-1)])
+        shuffle = rng.permutation(M)
+        rows = shuffle[rows]
+        row_deg = np.bincount(rows, minlength=M)
+    else:
+        rows, cols = configuration_model(rng, col_deg, row_deg)
     assert len(set((rows * N + cols).tolist())) == len(rows)
     assert np.array_equal(np.bincount(cols, minlength=N), col_deg)
     assert np.array_equal(np.bincount(rows, minlength=M), row_deg)

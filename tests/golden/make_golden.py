@@ -153,6 +153,16 @@ SYN_CASES = {
     # bp_kernel with global slots; bp_part_kernel at NG = 1040
     "syn_reg36_4080_16qam_blind": ("syn_reg36_4080.txt", "4bit_16QAM_Gray.txt", False, False, 20, 6.5, 24, True),
     "syn_reg36_4160_qpsk_known": ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, True, 20, 2.2, 24, True),
+    # bp_regular_kernel off PEG2304: another graph at K = 1152; then rank 1147,
+    # K = 1157 (Kw = 19, a partial last word): blind QPSK (the fused demap
+    # prologue), 16QAM (the separate demap) and the file-order graph; on the
+    # reference's stream 0.49, 0.43, 0.47 and 0.50 of the codewords run to max_iter
+    "syn_reg36_2304_qpsk_known": ("syn_reg36_2304.txt", "2bits_QPSK.txt", False, True, 20, 4.0, 100, True),
+    "syn_reg36_2304_r1147_qpsk_blind": ("syn_reg36_2304_r1147.txt", "2bits_QPSK.txt", False, False, 20, 4.0, 100, True),
+    "syn_reg36_2304_r1147_16qam_known": ("syn_reg36_2304_r1147.txt", "4bit_16QAM_Gray.txt", False, True, 20, 9.0, 100,
+                                         True),
+    "syn_reg36_2304_r1147_qpsk_known_inactive": ("syn_reg36_2304_r1147.txt", "2bits_QPSK.txt", False, True, 20, 4.0,
+                                                 100, False),
 }
 CASES.update(SYN_CASES)
 NVEC_CASE.update({"syn_reg36_4080_16qam_blind": 4, "syn_reg36_4160_qpsk_known": 4})

@@ -1,10 +1,11 @@
 // Host checks of the kernels' placement plans (layout.cpp) on the reference's
 // H files: every plan is a valid assignment of columns / rows / slots to lanes
 // with the properties the kernels rely on.  Prints "plan_errors=0" on success.
-//   plan_check <PEG2304 H> <BG2 H> <PEG8064 H> [--irregular F | --partition F | --none F]...
-// The extra (non-5G) H files are checked in the named role: the irregular
-// plan (with a census line of what its waves hold), the partition plan, or
-// neither plan being made (the code decodes on the generic bp_kernel).
+//   plan_check <PEG2304 H> <BG2 H> <PEG8064 H> [--regular F | --irregular F | --partition F | --none F]...
+// The extra (non-5G) H files are checked in the named role: the regular plan
+// of another PEG2304-class code, the irregular plan (with a census line of
+// what its waves hold), the partition plan, or neither plan being made (the
+// code decodes on the generic bp_kernel).
 // After each plan's checks one line pins the plan itself:
 //   digest <regular|irregular|partition> <H file name> <16 hex digits>
 // (tests/golden/host/plan_digests.json holds the recorded lines), and a
@@ -335,7 +336,10 @@ int main(int argc, char **argv) {
     LdpcCode x;
     if (!load(x, argv[i + 1], false)) return 2;
     const char *name = base_name(argv[i + 1]);
-    if (!strcmp(argv[i], "--irregular")) {
+    if (!strcmp(argv[i], "--regular")) {
+      CHECK(x.dv_max == 3 && x.dc_max == 6 && x.N == 2304 && x.M == 1152, "%s is not a PEG2304-class code", name);
+      check_regular(x, name);
+    } else if (!strcmp(argv[i], "--irregular")) {
       check_irregular(x, name, true);
     } else if (!strcmp(argv[i], "--partition")) {
       check_partition(x, name, false);

@@ -37,12 +37,16 @@ import pytest
 from oracle import oracle as O
 
 MATRIX = "PEG2304regular0.5.txt"
-# (modem file, snr): the three streams of the f32 mode's acceptance checks
+R1147 = "syn_reg36_2304_r1147.txt"  # the other PEG2304-class code: rank 1147, K = 1157 (tests/golden/make_codes.py)
+# (modem file, snr): the three streams of the f32 mode's acceptance checks, and
+# one on the rank-1147 code (QPSK at 4 dB: 0.43 of its codewords fail)
 STREAMS = {
     "qpsk": ("2bits_QPSK.txt", 2.0),
     "16qam": ("4bit_16QAM_Gray.txt", 8.0),
     "64qam": ("6bits_64QAM_Gray.txt", 13.0),
+    "r1147_qpsk": ("2bits_QPSK.txt", 4.0),
 }
+STREAM_MATRIX = {"r1147_qpsk": R1147}  # every other stream is on MATRIX
 CAP = 0.02        # share of codewords that may differ from the oracle (a condition, not a measurement)
 MIN_SHARE = 0.25  # each stream holds at least this share of converged and of failed codewords
 
@@ -159,10 +163,12 @@ def bp_model(g, p0, iter_count, max_iter, dtype=np.float32, division="ieee", see
 _cache = {}
 
 
-def oracle_code(data_dir, max_iter=20):
-    key = ("code", data_dir, max_iter)
+def oracle_code(data_dir, max_iter=20, name="qpsk"):
+    """The oracle's code and its graph for a stream's matrix."""
+    matrix = STREAM_MATRIX.get(name, MATRIX)
+    key = ("code", data_dir, max_iter, matrix)
     if key not in _cache:
-        oc = O.Code(os.path.join(data_dir, MATRIX), False, True, False, max_iter)
+        oc = O.Code(os.path.join(data_dir, matrix), False, True, False, max_iter)
         _cache[key] = (oc, Graph(oc))
     return _cache[key]
 
@@ -172,7 +178,7 @@ def stream(data_dir, name, n):
     key = ("stream", data_dir, name, n)
     if key not in _cache:
         modem, snr = STREAMS[name]
-        oc, _ = oracle_code(data_dir)
+        oc, _ = oracle_code(data_dir, name=name)
         om = O.Modem(os.path.join(data_dir, modem))
         uu, cc, th, y = O.gen_frames(oc, om, snr, n)
         var = 10.0 ** (-0.1 * snr)
@@ -190,7 +196,7 @@ def oracle_decode(data_dir, name, n, iter_count=20):
     """The oracle's decode of those n codewords at a budget (read-only, made once)."""
     key = ("dec", data_dir, name, n, iter_count)
     if key not in _cache:
-        oc, _ = oracle_code(data_dir)
+        oc, _ = oracle_code(data_dir, name=name)
         p0 = stream(data_dir, name, n)["p0"]
         ret = np.zeros(n, np.int32)
         uh = np.zeros((n, oc.K), np.uint8)
@@ -219,10 +225,19 @@ def differing(a, b):
 # ---- tests -----------------------------------------------------------------
 
 def test_float64_model_is_the_oracle(data_dir):
-    oc, g = oracle_code(data_dir)
+    _float64_model_is_the_oracle(data_dir, "qpsk", 256)
+
+
+def test_float64_model_is_the_oracle_at_rank_1147(data_dir):
+    """The same on the rank-1147 graph: uu_hat = cc_hat[chk : chk + K] with chk = 1147, K = 1157."""
+    _float64_model_is_the_oracle(data_dir, "r1147_qpsk", 192)
+
+
+def _float64_model_is_the_oracle(data_dir, name, n_stream):
+    oc, g = oracle_code(data_dir, name=name)
     n = 128
-    p0 = stream(data_dir, "qpsk", 256)["p0"][:n]  # (the 256 are shared with the float32 test)
-    ref = oracle_decode(data_dir, "qpsk", 256)
+    p0 = stream(data_dir, name, n_stream)["p0"][:n]  # (the stream is shared with the float32 test)
+    ref = oracle_decode(data_dir, name, n_stream)
     assert_both_outcomes(ref["ret"][:n])
     ret, uh, cch, syn = bp_model(g, p0, 20, 20, np.float64, "ieee", syn_init=SYN_FILL)
     assert np.array_equal(ret, ref["ret"][:n])
@@ -232,9 +247,9 @@ def test_float64_model_is_the_oracle(data_dir):
 
 
 @pytest.mark.parametrize("division", ["ieee", "rcp"])
-@pytest.mark.parametrize("name,n", [("qpsk", 256), ("16qam", 128), ("64qam", 128)])
+@pytest.mark.parametrize("name,n", [("qpsk", 256), ("16qam", 128), ("64qam", 128), ("r1147_qpsk", 192)])
 def test_float32_model_within_cap(data_dir, name, n, division):
-    oc, g = oracle_code(data_dir)
+    oc, g = oracle_code(data_dir, name=name)
     p0 = stream(data_dir, name, n)["p0"]
     ref = oracle_decode(data_dir, name, n)
     assert_both_outcomes(ref["ret"])
@@ -246,7 +261,7 @@ def test_float32_model_within_cap(data_dir, name, n, division):
 
 def model_syn_delta(data_dir, name, n, iter_count):
     """max |syn(float32 ieee model) - syn(oracle)| over the codewords whose ret agrees."""
-    oc, g = oracle_code(data_dir)
+    oc, g = oracle_code(data_dir, name=name)
     ref = oracle_decode(data_dir, name, n, iter_count)
     ret, _, _, syn = bp_model(g, stream(data_dir, name, n)["p0"], iter_count, 20, np.float32, "ieee",
                               syn_init=SYN_FILL)

@@ -3,8 +3,11 @@ kmldpc_amd/csrc/bp_regular_f32.hip).  The mode is not bit-exact with the
 reference: what it promises is agreement within a cap, independence of the
 batch, determinism, and that nothing of it leaks into the fp64 paths.
 
-The code is PEG2304 throughout (the kernel's only shape).  The streams, the
-oracle's decodes of them and the float32 model come from test_bp_f32_model.py.
+The code is PEG2304 (the kernel's only shape is its class: (3,6)-regular,
+2304 x 1152), and in one row or run of the decision, batch and demap tests the
+rank-1147 code of that class (K = 1157, 19 words of decoded bits, chk = 1147:
+tests/golden/make_codes.py).  The streams, the oracle's decodes of them and
+the float32 model come from test_bp_f32_model.py.
 """
 import os
 
@@ -13,7 +16,8 @@ import pytest
 
 from conftest import load_case
 from oracle import oracle as O
-from test_bp_f32_model import (CAP, MATRIX, STREAMS, SYN_FILL, assert_both_outcomes, differing, oracle_decode, stream)
+from test_bp_f32_model import (CAP, MATRIX, R1147, STREAM_MATRIX, STREAMS, SYN_FILL, assert_both_outcomes, differing,
+                               oracle_decode, stream)
 
 import kmldpc_amd as K
 
@@ -22,6 +26,7 @@ pytestmark = pytest.mark.gpu
 F32_KERNEL = "bp_regular_f32_kernel"
 F64_KERNEL = "bp_regular_kernel"
 N = 384  # codewords per stream
+N_R1147 = 96  # of the rank-1147 code's stream
 
 _ctx = {}
 
@@ -36,7 +41,7 @@ def ctx_for(data_dir, modem, matrix=MATRIX, is5g=False, max_iter=20):
 
 
 def f32_ctx(data_dir, name="qpsk"):
-    ctx = ctx_for(data_dir, STREAMS[name][0])
+    ctx = ctx_for(data_dir, STREAMS[name][0], STREAM_MATRIX.get(name, MATRIX))
     ctx.set_precision("f32")
     assert ctx.precision == "f32"
     return ctx
@@ -50,7 +55,15 @@ def f32_ctx(data_dir, name="qpsk"):
 #   16qam budget 20: 1.014e-03  64qam budget 20: 9.540e-04
 # (the reciprocal-multiply model with +-1 ulp reciprocals stays inside the
 # bounds too: 2.3e-07, 4.6e-04, 1.26e-03, 2.62e-03, 1.03e-03)
+# On the rank-1147 code's stream (96 codewords, QPSK at 4 dB) the budget-20
+# bound does not carry over: over 192 codewords the model itself sits 0.30 from
+# the oracle on one codeword whose ret agrees (a decode that diverges late),
+# against 1.2e-04 over the first 96, so the distance there measures the stream,
+# not the arithmetic.  Its syndromes are held at budget 1 (one CN phase, nothing
+# to diverge), where the model's value is
+#   r1147_qpsk budget 1: 1.238e-07
 SYN_BOUND = {
+    ("r1147_qpsk", 1): 4 * 1.238e-07,
     ("qpsk", 1): 4 * 1.281e-07,
     ("qpsk", 5): 4 * 1.423e-04,
     ("qpsk", 20): 4 * 5.409e-04,
@@ -59,8 +72,18 @@ SYN_BOUND = {
 }
 
 
-@pytest.mark.parametrize("name,budget", [("qpsk", 20), ("16qam", 20), ("64qam", 20), ("qpsk", 1), ("qpsk", 5)])
-def test_decisions_against_the_oracle(data_dir, name, budget):
+NO_SYN_BOUND = {("r1147_qpsk", 20)}  # every other row asserts its SYN_BOUND
+
+
+@pytest.mark.parametrize("matrix,name,budget,N", [
+    pytest.param(MATRIX, "qpsk", 20, N, id="qpsk-20"), pytest.param(MATRIX, "16qam", 20, N, id="16qam-20"),
+    pytest.param(MATRIX, "64qam", 20, N, id="64qam-20"), pytest.param(MATRIX, "qpsk", 1, N, id="qpsk-1"),
+    pytest.param(MATRIX, "qpsk", 5, N, id="qpsk-5"),
+    pytest.param(R1147, "r1147_qpsk", 20, N_R1147, id="r1147_qpsk-20"),
+    pytest.param(R1147, "r1147_qpsk", 1, N_R1147, id="r1147_qpsk-1"),
+])
+def test_decisions_against_the_oracle(data_dir, matrix, name, budget, N):
+    assert STREAM_MATRIX.get(name, MATRIX) == matrix
     ctx = f32_ctx(data_dir, name)
     p0 = stream(data_dir, name, N)["p0"]
     ref = oracle_decode(data_dir, name, N, budget)
@@ -73,12 +96,15 @@ def test_decisions_against_the_oracle(data_dir, name, budget):
     d_cc = differing(r["cc_hat"], ref["cc_hat"])
     same = ~d_ret
     d_syn = float(np.max(np.abs(r["syn"][same] - ref["syn"][same])))
+    bound = None if (name, budget) in NO_SYN_BOUND else SYN_BOUND[(name, budget)]
     print(f"{name} budget {budget}: codewords differing in uu_hat {int(d_uu.sum())}, ret {int(d_ret.sum())}, "
-          f"cc_hat {int(d_cc.sum())} of {N}; max |syn - oracle| {d_syn:.3e} (bound {SYN_BOUND[(name, budget)]:.3e})")
+          f"cc_hat {int(d_cc.sum())} of {N}; max |syn - oracle| {d_syn:.3e} (bound {bound})")
+    assert (ctx.K, ctx.chk) == ((1157, 1147) if matrix == R1147 else (1152, 1152))
     assert d_uu.mean() <= CAP
     assert d_ret.mean() <= CAP
     assert d_cc.mean() <= CAP
-    assert d_syn <= SYN_BOUND[(name, budget)]
+    if bound is not None:
+        assert d_syn <= bound
 
 
 def test_batch_and_queue_independence(data_dir):
@@ -96,6 +122,23 @@ def test_batch_and_queue_independence(data_dir):
         # the second copy of the stream sits at other queue positions
         assert np.array_equal(runs["700"][key][N:700], runs["700"][key][:700 - N]), key
     assert np.any(runs["700"]["ret"] == 20) and np.any(runs["700"]["ret"] < 20)
+
+
+def test_batch_independence_at_rank_1147(data_dir):
+    """The same on the rank-1147 code (uu_hat rows of 1157 bytes): B = 1, 3 and 96, the stream's first 48 twice."""
+    ctx = f32_ctx(data_dir, "r1147_qpsk")
+    p0 = stream(data_dir, "r1147_qpsk", N_R1147)["p0"][:48]
+    big = np.concatenate([p0, p0])
+    runs = {}
+    for tag, B in [("1", 1), ("3", 3), ("96", 96), ("96 again", 96)]:
+        runs[tag] = ctx.bp_decode(big[:B], 20, cc_hat=True, syn=np.full((B, ctx.M), SYN_FILL))
+        assert ctx.bp_kernel() == F32_KERNEL
+    for key in ("uu_hat", "ret", "cc_hat", "syn"):
+        assert np.array_equal(runs["96"][key], runs["96 again"][key]), key
+        assert np.array_equal(runs["1"][key], runs["96"][key][:1]), key
+        assert np.array_equal(runs["3"][key], runs["96"][key][:3]), key
+        assert np.array_equal(runs["96"][key][48:], runs["96"][key][:48]), key
+    assert np.any(runs["96"]["ret"] == 20) and np.any(runs["96"]["ret"] < 20)
 
 
 def _check_golden_f64(ctx, z):
@@ -129,9 +172,16 @@ def test_no_leakage_between_modes(data_dir):
 
 
 def test_fused_and_separate_demap_agree(data_dir):
-    ctx = f32_ctx(data_dir)
-    s = stream(data_dir, "qpsk", N)
-    n = 256
+    _fused_and_separate_demap_agree(data_dir, "qpsk", N, 256)
+
+
+def test_fused_and_separate_demap_agree_at_rank_1147(data_dir):
+    _fused_and_separate_demap_agree(data_dir, "r1147_qpsk", N_R1147, N_R1147)
+
+
+def _fused_and_separate_demap_agree(data_dir, name, N, n):
+    ctx = f32_ctx(data_dir, name)
+    s = stream(data_dir, name, N)
     y, th = s["y"][:n], s["th"][:n]
     fused = ctx.decode_frames(y, s["snr"], th)
     assert ctx.bp_kernel() == F32_KERNEL
@@ -198,6 +248,23 @@ def test_other_codes_refuse_f32(data_dir, case):
     assert ctx.precision == "f64"
     _check_golden_f64(ctx, z)
     assert ctx.bp_kernel() != F32_KERNEL
+
+
+@pytest.mark.parametrize("case", ["syn_reg36_2304_qpsk_known", "syn_reg36_2304_r1147_16qam_known"])
+def test_peg2304_class_codes_accept_f32(data_dir, case):
+    """The counter-case: any (3,6)-regular 2304 x 1152 code takes the mode, full rank or not, and leaves it again."""
+    hdr, z = load_case(case)
+    ctx = ctx_for(data_dir, hdr["modem"], hdr["matrix"], False, hdr["max_iter"])
+    ctx.set_precision("f32")
+    assert ctx.precision == "f32"
+    B = z["v_p0"].shape[0]
+    r = ctx.bp_decode(z["v_p0"], cc_hat=True, syn=np.full((B, ctx.M), -1.0))
+    assert ctx.bp_kernel() == F32_KERNEL
+    assert r["ret"].min() >= 1 and r["ret"].max() <= 20
+    ctx.set_precision("f64")
+    assert ctx.precision == "f64"
+    _check_golden_f64(ctx, z)
+    assert ctx.bp_kernel() == F64_KERNEL
 
 
 def test_unknown_precision_is_an_argument_error(data_dir):

@@ -6,7 +6,7 @@ var), iter_count=k) counted against uu, and contexts created with max_iter = k.
 Every comparison is an exact equality.
 
 Frames come from O.gen_frames with the oracle's own seed (17).  The streams of
-the four cases hold no codeword that converges at iteration 0 (the channel is
+the cases hold no codeword that converges at iteration 0 (the channel is
 a per-codeword fading h; measured with the oracle: PEG2304 / QPSK at 2 dB
 converges at iterations 1..7 or not at all within 8), so the last 16 of the 96
 frames of every case are noise-free frames (60 dB, seed 18) received at the
@@ -43,6 +43,8 @@ pytestmark = pytest.mark.gpu
 
 PEG, PEG8064, BG2 = "PEG2304regular0.5.txt", "PEG8064regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt"
 IRR = "syn_irr1200.txt"  # non-5G irregular, every column degree 1..9 and row degree 2..10 (tests/golden/make_codes.py)
+# PEG2304-class, rank 1147: K = 1157, so the PROF instances' per-iteration error count has a partial last word
+R1147 = "syn_reg36_2304_r1147.txt"
 QPSK, QAM16, QAM64 = "2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt"
 # name: matrix, modem, 5G, Es/N0, environment
 CASES = {
@@ -51,6 +53,8 @@ CASES = {
     "peg_16qam": (PEG, QAM16, False, 8.0, {}),
     "bg2_16qam": (BG2, QAM16, True, 9.0, {}),  # the oracle fails 61 % of the seed-17 codewords within 8 iterations
     "syn_irr1200_qpsk": (IRR, QPSK, False, 4.0, {}),  # the PROF instances of the degrees BG2 does not have
+    "r1147_qpsk_fused": (R1147, QPSK, False, 4.0, {}),
+    "r1147_qpsk_unfused": (R1147, QPSK, False, 4.0, {"KML_FUSED_DEMAP": "0"}),
 }
 UNSUP = "(code -4)"
 
@@ -153,6 +157,8 @@ def test_per_budget_equality_and_plain_path(env, monkeypatch, case):
     cw_err, _, plain_ex = ctx.sim_decode_ex(snr, blind=False)
     prof, cwp, cnt = ctx.sim_decode_profile(snr, blind=False)
     assert ctx.bp_kernel() == ("bp_irregular_kernel" if is5g or matrix == IRR else "bp_regular_kernel")
+    if matrix == R1147:
+        assert ctx.K == 1157 and ctx.chk == 1147
     _check_rows(prof, cwp, err, ret, plain["converged"], P)
     # the ordinary outputs of the profile call are the plain call's
     assert cnt == plain == plain_ex

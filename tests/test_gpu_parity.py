@@ -33,6 +33,10 @@ _ctx = {}
 BPSK, PSK8, STAR8 = "syn_1bit_BPSK.txt", "syn_3bits_8PSK_Gray.txt", "syn_3bits_star8.txt"
 MODEMS = ["2bits_QPSK.txt", "4bit_16QAM_Gray.txt", "6bits_64QAM_Gray.txt", BPSK, PSK8, STAR8]
 # S = 2304 and 768 on PEG2304, S = 64 (exactly one k-means word), S = 400 (a partial last word)
+# The PEG2304-class synthetic codes (tests/golden/make_codes.py): (3,6)-regular,
+# 2304 x 1152, so the dispatcher sends them to bp_regular_kernel; full rank, and
+# rank 1147 (K = 1157: 19 words of decoded bits, the last holds five; chk = 1147)
+REG2304, R1147 = "syn_reg36_2304.txt", "syn_reg36_2304_r1147.txt"
 SYN_CONS_ROWS = [("PEG2304regular0.5.txt", BPSK, 0.5), ("PEG2304regular0.5.txt", PSK8, 5.0),
                  ("PEG2304regular0.5.txt", STAR8, 8.0), ("syn_reg36_192.txt", PSK8, 8.0),
                  ("syn_irr1200.txt", STAR8, 8.0)]
@@ -312,6 +316,11 @@ def test_bp_golden_vectors(case, data_dir):
     ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, 2.2, 20, 24),
     ("syn_irr1200.txt", "6bits_64QAM_Gray.txt", False, 10.0, 30, 64),
     ("syn_reg36_4080.txt", "6bits_64QAM_Gray.txt", False, 10.0, 20, 24),
+    # bp_regular_kernel off PEG2304: another graph at K = 1152, then rank 1147
+    # (K = 1157, chk = 1147) behind the oracle's QPSK and 16QAM priors
+    (REG2304, "2bits_QPSK.txt", False, 4.0, 20, 64),
+    (R1147, "2bits_QPSK.txt", False, 4.0, 20, 64),
+    (R1147, "4bit_16QAM_Gray.txt", False, 9.0, 20, 48),
 ])
 def test_bp_vs_oracle_stream(data_dir, matrix, modem, is5g, snr, max_iter, n):
     """Oracle frames -> oracle P0 -> GPU BP vs oracle BP, bit-exact incl. the
@@ -412,22 +421,27 @@ def test_demap_and_metric_adversarial(data_dir, matrix, modem, snr):
     assert np.array_equal(c1["metrics"], out["metrics"]) and not c1["ret"].any()
 
 
-@pytest.mark.parametrize("blind", [False, True])
-def test_fused_demap_matches_separate(data_dir, blind, monkeypatch):
-    """Known-channel and chosen-candidate QPSK decodes on the regular code run
+@pytest.mark.parametrize("matrix,snr,blind", [
+    pytest.param("PEG2304regular0.5.txt", 2.0, False, id="False"),
+    pytest.param("PEG2304regular0.5.txt", 2.0, True, id="True"),
+    pytest.param(R1147, 4.0, False, id="r1147-False"), pytest.param(R1147, 4.0, True, id="r1147-True")])
+def test_fused_demap_matches_separate(data_dir, matrix, snr, blind, monkeypatch):
+    """Known-channel and chosen-candidate QPSK decodes on the regular codes run
     the demap in the BP kernel's prologue; KML_FUSED_DEMAP=0 runs the separate
     demap kernel: every output is identical (and the oracle agrees)."""
-    ctx = ctx_for(data_dir, "PEG2304regular0.5.txt", "2bits_QPSK.txt", False)
-    oc = oracle_for(data_dir, "PEG2304regular0.5.txt", False)
+    ctx = ctx_for(data_dir, matrix, "2bits_QPSK.txt", False)
+    oc = oracle_for(data_dir, matrix, False)
     om = O.Modem(os.path.join(data_dir, "2bits_QPSK.txt"))
-    uu, cc, th, y = O.gen_frames(oc, om, 2.0, 96, state=23)
-    r1 = ctx.decode_frames(y, 2.0, None if blind else th)
+    uu, cc, th, y = O.gen_frames(oc, om, snr, 96, state=23)
+    r1 = ctx.decode_frames(y, snr, None if blind else th)
+    assert ctx.bp_kernel() == "bp_regular_kernel"
     monkeypatch.setenv("KML_FUSED_DEMAP", "0")
-    r0 = ctx.decode_frames(y, 2.0, None if blind else th)
+    r0 = ctx.decode_frames(y, snr, None if blind else th)
+    assert ctx.bp_kernel() == "bp_regular_kernel"
     for k in ("uu_hat", "chosen", "ret", "metrics"):
         assert np.array_equal(r1[k], r0[k]), k
     for i in range(0, 96, 8):
-        ref = O.receive(oc, om, y[i], th[i], 2.0, blind)
+        ref = O.receive(oc, om, y[i], th[i], snr, blind)
         assert np.array_equal(r1["uu_hat"][i], ref["uu_hat"]) and r1["ret"][i] == ref["ret"], i
 
 
@@ -621,20 +635,23 @@ FAMILY = {"PEG2304regular0.5.txt": "bp_regular_kernel", "5GLDPCBG2a3_R12_K960.tx
 # The synthetic codes (tests/golden/make_codes.py), with the constellation and
 # max_iter of their reference fixtures (so the contexts are shared), and the
 # family each must decode on: the generic bp_kernel is the native path of every
-# regular code that is neither PEG2304-class nor tiled by the partitioned kernel.
+# regular code that is neither PEG2304-class nor tiled by the partitioned kernel;
+# the PEG2304-class ones, whatever their graph and rank, go to bp_regular_kernel.
 SYN_CODES = [("syn_irr1200.txt", "2bits_QPSK.txt", False, 30),       # every degree instance, non-5G
              ("syn_reg36_192.txt", "2bits_QPSK.txt", False, 20),     # bp_kernel<3,6> in LDS
              ("syn_reg48_240.txt", "4bit_16QAM_Gray.txt", False, 20),  # bp_kernel<12,12> in LDS, rank-deficient
              ("syn_high120.txt", "2bits_QPSK.txt", False, 20),       # bp_kernel<32,32> in LDS
              ("syn_reg36_4080.txt", "4bit_16QAM_Gray.txt", False, 20),  # bp_kernel<3,6>, global slots
-             ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, 20)]    # bp_part_kernel, NG = 1040
+             ("syn_reg36_4160.txt", "2bits_QPSK.txt", False, 20),    # bp_part_kernel, NG = 1040
+             (R1147, "2bits_QPSK.txt", False, 20)]                   # bp_regular_kernel, K = 1157
+REG_CODES = [(REG2304, "2bits_QPSK.txt", False, 20)]                 # bp_regular_kernel, another graph at K = 1152
 FAMILY.update({"syn_irr1200.txt": "bp_irregular_kernel", "syn_reg36_192.txt": "bp_kernel",
                "syn_reg48_240.txt": "bp_kernel", "syn_high120.txt": "bp_kernel", "syn_reg36_4080.txt": "bp_kernel",
-               "syn_reg36_4160.txt": "bp_part_kernel"})
+               "syn_reg36_4160.txt": "bp_part_kernel", REG2304: "bp_regular_kernel", R1147: "bp_regular_kernel"})
 SYN_LARGE = ("syn_reg36_4080.txt", "syn_reg36_4160.txt")
 
 
-@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES + SYN_CODES)
+@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES + SYN_CODES + REG_CODES)
 def test_dispatch_takes_the_specialised_kernel(data_dir, matrix, modem, is5g, max_iter):
     """Each code runs on its own kernel family (so the parity tests below cover
     all of them): the shipped codes on the three specialised ones, never on the
@@ -755,7 +772,7 @@ def test_irregular_kernel_deferral_beside_fast_codewords(data_dir):
 
 @pytest.mark.parametrize("matrix,modem,is5g,max_iter", SYN_CODES)
 def test_counters_with_a_partial_last_word(data_dir, matrix, modem, is5g, max_iter):
-    """K off the 64-bit grid (600, 96, 121, 60, 2040, 2080): the error-count
+    """K off the 64-bit grid (600, 96, 121, 60, 2040, 2080, 1157): the error-count
     epilogues' partial last word (nb = min(64, K - base)) and the packed
     reference bits.  Oracle frames loaded as the resident batch; the counters
     of kml_sim_decode and the per-codeword error bits of kml_sim_decode_ex
@@ -764,7 +781,7 @@ def test_counters_with_a_partial_last_word(data_dir, matrix, modem, is5g, max_it
     oc = oracle_for(data_dir, matrix, is5g, max_iter)
     om = O.Modem(os.path.join(data_dir, modem))
     snr = {"syn_irr1200.txt": 2.0, "syn_reg36_192.txt": 3.0, "syn_reg48_240.txt": 8.5, "syn_high120.txt": 2.0,
-           "syn_reg36_4080.txt": 6.5, "syn_reg36_4160.txt": 2.2}[matrix]
+           "syn_reg36_4080.txt": 6.5, "syn_reg36_4160.txt": 2.2, R1147: 4.0}[matrix]
     n = 24 if matrix in SYN_LARGE else 48
     assert ctx.K % 64 != 0 and ctx.K == oc.K
     uu, cc, th, y = O.gen_frames(oc, om, snr, n, state=41)
@@ -816,7 +833,7 @@ def test_generic_kernel_on_the_shipped_codes(data_dir):
     assert r.stdout.count("bp_kernel ok") == 3, r.stdout
 
 
-@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES)
+@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES + SYN_CODES[-1:])
 def test_empty_and_ragged_batches(data_dir, matrix, modem, is5g, max_iter):
     ctx = ctx_for(data_dir, matrix, modem, is5g, max_iter)
     r = ctx.bp_decode(np.zeros((0, ctx.cc_len)))
@@ -832,7 +849,7 @@ def test_empty_and_ragged_batches(data_dir, matrix, modem, is5g, max_iter):
             assert r["ret"][i] == ret and np.array_equal(r["uu_hat"][i], uh)
 
 
-@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES)
+@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES + SYN_CODES[-1:])
 def test_extreme_inputs_match_oracle(data_dir, matrix, modem, is5g, max_iter):
     """Saturated / tie / NaN-free edge inputs: P0 at the clip bounds, exactly
     0.5 everywhere (every hard decision is a tie -> 1), 0/1 extremes, and -0.0
@@ -854,7 +871,7 @@ def test_extreme_inputs_match_oracle(data_dir, matrix, modem, is5g, max_iter):
         assert np.array_equal(r["syn"][i], syn, equal_nan=True), i
 
 
-@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES)
+@pytest.mark.parametrize("matrix,modem,is5g,max_iter", CODES + SYN_CODES[-1:])
 def test_nan_and_inf_priors_match_oracle(data_dir, matrix, modem, is5g, max_iter):
     """NaN and +-inf priors (the IEEE path): the messages then carry NaNs, whose
     sign bits the decision-in-sign-bit parity (bp_regular / bp_irregular) must
@@ -1160,7 +1177,8 @@ EXACT_MODES = ["KML_NO_FAST", "KML_FORCE_REDO"]
 @pytest.mark.parametrize("mode", EXACT_MODES)
 @pytest.mark.parametrize("case", ["peg2304_qpsk_known", "bg2_16qam_known", "peg8064_64qam_known",
                                   "peg2304_4psk_known_lowsnr", "syn_irr1200_qpsk_known",
-                                  "syn_reg36_4160_qpsk_known", "peg2304_bpsk_blind", "peg2304_8psk_known"])
+                                  "syn_reg36_4160_qpsk_known", "peg2304_bpsk_blind", "peg2304_8psk_known",
+                                  "syn_reg36_2304_r1147_16qam_known", "syn_reg36_2304_qpsk_known"])
 def test_exact_path_golden_vectors(case, data_dir, mode, monkeypatch):
     hdr, z = load_case(case)
     monkeypatch.setenv(mode, "1")
@@ -1181,7 +1199,7 @@ def test_exact_path_golden_vectors(case, data_dir, mode, monkeypatch):
 
 @pytest.mark.parametrize("mode", EXACT_MODES)
 @pytest.mark.parametrize("case", ["peg2304_qpsk_known", "peg2304_qpsk_blind", "bg2_16qam_blind", "peg8064_64qam_blind",
-                                  "peg2304_bpsk_blind", "peg2304_8psk_known"])
+                                  "peg2304_bpsk_blind", "peg2304_8psk_known", "syn_reg36_2304_r1147_qpsk_blind"])
 def test_exact_path_reference_stream(case, data_dir, mode, monkeypatch):
     """KmCodec::Decoder on the reference's frames through the exact path and
     through forced redos (fused QPSK demap prologue included): chosen
@@ -1252,6 +1270,8 @@ def test_candidate_metric_screen_equals_exact_demap(data_dir, modem, monkeypatch
     # bp_regular_kernel, and unequal moduli in front of bp_irregular_kernel
     ("PEG2304regular0.5.txt", BPSK, False, 0.5, 100),
     ("syn_irr1200.txt", STAR8, False, 8.0, 64),
+    # the rank-1147 PEG2304-class code: four candidates and the fused demap prologue at K = 1157
+    (R1147, "2bits_QPSK.txt", False, 4.0, 64),
 ])
 def test_cross_product_blind_streams_vs_oracle(data_dir, matrix, modem, is5g, snr, n):
     """The (code x constellation) pairs beyond the reference fixtures' 40-100

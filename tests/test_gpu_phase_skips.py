@@ -3,7 +3,9 @@ the VN phase of iteration 0 in closed form on the FAST path
 (every v2c is the prior pair, tests/test_iter0_model.py)
 and the budget's last CN phase reduced to its parity check when no syndromes
 are asked for.  Every output stays the reference's bit
-for bit: PEG2304 + QPSK (N = 2304 is the only shape this kernel takes) against
+for bit: PEG2304 + QPSK (N = 2304 is the only shape this kernel takes), and the
+rank-1147 code of the same shape (K = 1157, chk = 1147: a partial last word of
+decoded bits and another graph; the r1147 cases), against
 the oracle's BP decode of the same priors and the oracle's receive path, with
 iteration budgets that put the shortcuts in the same, in neighbouring and in
 distant iterations, with and without syndrome output, on the FAST path, through
@@ -22,6 +24,7 @@ import kmldpc_amd as K
 pytestmark = pytest.mark.gpu
 
 MATRIX, MODEM = "PEG2304regular0.5.txt", "2bits_QPSK.txt"
+R1147 = "syn_reg36_2304_r1147.txt"  # tests/golden/make_codes.py
 SNR = 2.0  # the headline workload's Es/N0
 MODES = ["fast", "KML_FORCE_REDO", "KML_NO_FAST"]
 BUDGETS = [1, 2, 20]
@@ -29,11 +32,11 @@ LO = math.ldexp(1.0, 40 * 3 - 960)  # bp_common.hpp fast_prior_lo(dv = 3)
 
 
 class Env:
-    def __init__(self, data_dir):
-        mk = lambda it: K.Context(matrix_file=os.path.join(data_dir, MATRIX), modem_file=os.path.join(data_dir, MODEM),
+    def __init__(self, data_dir, matrix=MATRIX):
+        mk = lambda it: K.Context(matrix_file=os.path.join(data_dir, matrix), modem_file=os.path.join(data_dir, MODEM),
                                   max_iter=it, device=0)
         self.ctx = {20: mk(20), 1: mk(1)}
-        self.oc = {it: O.Code(os.path.join(data_dir, MATRIX), False, True, False, it) for it in (20, 1)}
+        self.oc = {it: O.Code(os.path.join(data_dir, matrix), False, True, False, it) for it in (20, 1)}
         self.om = O.Modem(os.path.join(data_dir, MODEM))
         self._batches = {}
         self._ref = {}
@@ -119,10 +122,22 @@ class Env:
 
 
 @pytest.fixture(scope="module")
-def env(data_dir):
-    e = Env(data_dir)
-    yield e
-    e.close()
+def envs(data_dir):
+    """One Env per code, made when a case first asks for it."""
+    made = {}
+
+    def get(code):
+        if code not in made:
+            made[code] = Env(data_dir, {"peg": MATRIX, "r1147": R1147}[code])
+        return made[code]
+    yield get
+    for e in made.values():
+        e.close()
+
+
+@pytest.fixture(scope="module")
+def env(envs):
+    return envs("peg")
 
 
 def _set_mode(monkeypatch, mode):
@@ -132,13 +147,16 @@ def _set_mode(monkeypatch, mode):
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("it", BUDGETS)
-@pytest.mark.parametrize("name", ["noisy", "clean", "adversarial", "mixed"])
-def test_bp_decode_matches_oracle(env, monkeypatch, name, it, mode):
+@pytest.mark.parametrize("name", ["noisy", "clean", "adversarial", "mixed",
+                                  "r1147_noisy", "r1147_clean", "r1147_adversarial", "r1147_mixed"])
+def test_bp_decode_matches_oracle(envs, monkeypatch, name, it, mode):
     """ret, uu_hat, cc_hat bit for bit without syndrome output (the last CN
     phase is the parity check alone) and with it (the last CN phase still
     writes the reference's syndromes).  Budget 1 puts both shortcuts in the
     same iteration."""
     _set_mode(monkeypatch, mode)
+    env = envs("r1147" if name.startswith("r1147_") else "peg")
+    name = name.removeprefix("r1147_")
     ctx = env.ctx[20]
     p0 = env.batch(name)
     B = p0.shape[0]
@@ -178,8 +196,10 @@ def test_noise_free_frames_count_no_cn_phase(env, monkeypatch, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("max_iter", [20, 1])
-def test_fused_demap_path_and_counters(env, monkeypatch, max_iter, mode):
+@pytest.mark.parametrize("code,max_iter", [pytest.param("peg", 20, id="20"), pytest.param("peg", 1, id="1"),
+                                           pytest.param("r1147", 20, id="r1147-20"),
+                                           pytest.param("r1147", 1, id="r1147-1")])
+def test_fused_demap_path_and_counters(envs, monkeypatch, code, max_iter, mode):
     """Known-H frames through the fused-demap launch (SYN = false, the headline
     kernel) at the configured max_iter and with a context configured for
     max_iter = 1, against the oracle's receive path; and the resident-batch
@@ -190,9 +210,12 @@ def test_fused_demap_path_and_counters(env, monkeypatch, max_iter, mode):
     is both "converged at the last iteration" and "exhausted": the parity of the
     oracle's final decisions tells them apart."""
     _set_mode(monkeypatch, mode)
+    env = envs(code)
     ctx = env.ctx[max_iter]
+    assert (ctx.K, ctx.chk) == ((1157, 1147) if code == "r1147" else (1152, 1152))
     (uu, cc, th, y), ref = env.rx(max_iter)
     r = ctx.decode_frames(y, SNR, th)
+    assert ctx.bp_kernel() == "bp_regular_kernel"
     for i in range(64):
         assert r["ret"][i] == ref[i]["ret"], i
         assert np.array_equal(r["uu_hat"][i], ref[i]["uu_hat"]), i

@@ -28,11 +28,14 @@ CODES = [
     ("syn_high120.txt", False),
     ("syn_reg36_4080.txt", False),
     ("syn_reg36_4160.txt", False),
+    ("syn_reg36_2304.txt", False),
+    ("syn_reg36_2304_r1147.txt", False),
 ]
 SHIPPED = ("PEG2304regular0.5.txt", "5GLDPCBG2a3_R12_K960.txt", "PEG8064regular0.5.txt")
 # plan_check's extra H files and their roles: the plan each synthetic code takes
 SYN_PLAN_ARGS = [("--irregular", "syn_irr1200.txt"), ("--none", "syn_reg36_192.txt"), ("--none", "syn_reg48_240.txt"),
-                 ("--none", "syn_high120.txt"), ("--none", "syn_reg36_4080.txt"), ("--partition", "syn_reg36_4160.txt")]
+                 ("--none", "syn_high120.txt"), ("--none", "syn_reg36_4080.txt"), ("--partition", "syn_reg36_4160.txt"),
+                 ("--regular", "syn_reg36_2304.txt"), ("--regular", "syn_reg36_2304_r1147.txt")]
 
 
 def plan_check_args(data_dir):
@@ -93,6 +96,8 @@ def test_planner_matches_oracle(data_dir, matrix, is5g, active):
                                                                            oc.chk)
     if matrix == "syn_reg48_240.txt" and active:  # rank-deficient: the (4,8) rows sum to zero
         assert ctx.chk == 119 and ctx.K == 121
+    if matrix == "syn_reg36_2304_r1147.txt" and active:  # rank-deficient: five pairs of identical rows
+        assert ctx.chk == 1147 and ctx.K == 1157
     assert np.array_equal(ctx.perm(), oc.perm())
     for a, b in zip(ctx.graph(), oc.graph()):
         assert np.array_equal(a, b)
@@ -236,8 +241,9 @@ def test_kernel_placement_plans(tmp_path, data_dir):
     reference's H files: bp_regular's interleaved row slots and c2v halves,
     bp_irregular's paired rounds (each column / row once, pairs of one degree
     within the limits, one degree per paired wave), bp_part's partition; and
-    on the synthetic codes in the role each was built for (an irregular plan, a
-    partition plan, or neither)."""
+    on the synthetic codes in the role each was built for (a regular plan on a
+    second and a third PEG2304-class graph, an irregular plan, a partition
+    plan, or neither)."""
     exe = tmp_path / "planc"
     csrc = os.path.join(REPO, "kmldpc_amd", "csrc")
     subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I", csrc, "-o", str(exe),
