@@ -138,6 +138,50 @@ enum { KML_PREC_F64 = 0, KML_PREC_F32 = 1 };
 int kml_set_precision(kml_ctx *ctx, int prec);
 int kml_get_precision(const kml_ctx *ctx);
 
+/* Decoding algorithm of the final BP decodes, per context.  KML_ALG_SPA (the
+ * default) is the reference's sum-product decoder, bit-exact; it is always
+ * accepted and alpha is ignored.  KML_ALG_NMS is an opt-in normalized min-sum
+ * decoder for the codes that take bp_irregular_kernel (5G BG2 K960 and other
+ * irregular codes whose messages fit in LDS; "bp_irregular_nms_kernel" in
+ * kml_bp_kernel).  It is a different decoder: its results are NOT the
+ * reference's.  What is fixed instead is its arithmetic, which
+ * tests/bp_nms_model.py restates in numpy and the kernel equals bit for bit
+ * (uu_hat, ret, cc_hat).  Every value is IEEE binary32 with denormals kept, no
+ * fma, each operation rounded once:
+ *   prior     q = min(max(P0, 1e-12), 1 - 1e-12) in fp64,
+ *             L = (float)(log(q) - log(1 - q)) (fp64 logs and subtraction);
+ *             a punctured 5G column has L = +0; messages start at +0;
+ *   VN phase  column v, edges in column order (kml_code_graph's col_ptr /
+ *             col_slot): t = L; t = t + c2v_k for every k in order; T = t;
+ *             decision T > 0 ? 0 : 1 (a tie decides 1);
+ *             v2c_k = clamp(T - c2v_k, -256.0f, 256.0f);
+ *   stop      after the VN phase, when every check row's decisions have even
+ *             parity, before the CN phase; ret = iter + (iter < max_iter);
+ *             iter_count = 0 leaves uu_hat / cc_hat as passed;
+ *   CN phase  row with incoming m_j: a_j = min over i != j of |m_i|,
+ *             s_j = XOR over i != j of the IEEE sign bits of m_i (-0 counts as
+ *             negative), c2v_j = RN(alpha * a_j) with its sign bit set to s_j.
+ * alpha is the normalisation factor: 0 selects the default 0.75, otherwise
+ * 0 < alpha <= 1, rounded once to float (1 is plain min-sum); any other value,
+ * NaN included, and an unknown alg return KML_E_ARG.
+ * The scope is that of kml_set_precision: the final decode of kml_bp_decode,
+ * kml_decode_frames, kml_decode_candidates, kml_sim_decode(_ex) and
+ * kml_sim_point; k-means, the demapper and the candidate metrics (BG2's
+ * metric_iter decodes included) stay fp64 sum-product, so chosen, metrics and
+ * h_hat are bit-identical in both algorithms.  CNT_REDONE stays 0;
+ * kml_prof_read_flops keeps applying the sum-product rule and is not
+ * meaningful in this mode.
+ * KML_E_UNSUP, with the context's algorithm unchanged: a host-only context, a
+ * code that does not take bp_irregular_kernel (PEG2304, PEG8064 and the
+ * generic-kernel codes), a context in the f32 precision (a guard: no code takes
+ * both kernels), and KML_BP_KERNEL=generic.  In NMS mode a non-NULL
+ * syn (min-sum has no syndrom_soft), the soft-syndrome metric (metric_type =
+ * 1) and kml_sim_decode_profile return KML_E_UNSUP before anything is
+ * launched.  There is no fallback in either direction. */
+enum { KML_ALG_SPA = 0, KML_ALG_NMS = 1 };
+int kml_set_algorithm(kml_ctx *ctx, int alg, double alpha);
+int kml_get_algorithm(const kml_ctx *ctx, double *alpha /* may be NULL */);
+
 int kml_dims(const kml_ctx *ctx, int32_t *dims /* [KML_DIM_COUNT] */);
 /* Host-side code plan, for inspection and parity tests. */
 int kml_code_perm(const kml_ctx *ctx, int32_t *perm /* [Ncol] */);

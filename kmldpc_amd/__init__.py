@@ -31,6 +31,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include", "kmldpc_amd.h")
 KML_DEVICE_PTRS = 1
 KML_HISTOGRAM = 2
 PRECISIONS = {"f64": 0, "f32": 1}  # KML_PREC_F64, KML_PREC_F32
+ALGORITHMS = {"spa": 0, "nms": 1}  # KML_ALG_SPA, KML_ALG_NMS
 DIM_NAMES = ["M", "Ncol", "K", "cc_len", "Z", "E", "chk", "max_iter", "bits", "Kc", "S", "bp_lds", "part_group"]
 
 
@@ -79,6 +80,8 @@ def lib():
         "kml_bp_kernel": (C.c_char_p, [P]),
         "kml_set_precision": (I, [P, I]),
         "kml_get_precision": (I, [P]),
+        "kml_set_algorithm": (I, [P, I, D]),
+        "kml_get_algorithm": (I, [P, P]),
         "kml_create": (I, [C.c_char_p, C.c_char_p, I, PP]),
         "kml_create_explicit": (I, [C.c_char_p, C.c_char_p, I, I, I, I, I, I, PP]),
         "kml_destroy": (None, [P]),
@@ -149,6 +152,14 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _parse_algorithm(spec):
+    """"spa", "nms" or "nms:alpha" (the drivers' --algorithm / KML_ALGORITHM spelling) -> (name, alpha or None)."""
+    name, colon, alpha = str(spec).partition(":")
+    if colon and not alpha:
+        raise ValueError(f"algorithm {spec!r}: alpha missing after ':'")
+    return name, (float(alpha) if colon else None)
+
+
 def _f64(a, shape=None):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if shape is not None:
@@ -160,7 +171,7 @@ class Context:
     """One code + modem on one GPU (device < 0: host-only planner context)."""
 
     def __init__(self, config=None, data_dir=None, device=0, *, matrix_file=None, modem_file=None, is5g=False,
-                 active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64"):
+                 active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64", algorithm="spa"):
         L = lib()
         h = C.c_void_p()
         if config is not None:
@@ -188,6 +199,12 @@ class Context:
         if precision != "f64":
             try:
                 self.set_precision(precision)
+            except Exception:
+                self.close()
+                raise
+        if algorithm != "spa":
+            try:
+                self.set_algorithm(*_parse_algorithm(algorithm))
             except Exception:
                 self.close()
                 raise
@@ -226,6 +243,26 @@ class Context:
     def precision(self):
         v = int(lib().kml_get_precision(self._h))
         return {n: k for k, n in PRECISIONS.items()}[v]
+
+    # ---- decoding algorithm (kml_set_algorithm)
+    def set_algorithm(self, algorithm, alpha=None):
+        """"spa" (default: the reference's sum-product, bit-exact) or "nms" (opt-in normalized min-sum
+        for the codes of bp_irregular_kernel, e.g. 5G BG2; its results are not the reference's, its
+        arithmetic is tests/bp_nms_model.py's bit for bit).  alpha: the normalisation factor in (0, 1],
+        None = the default 0.75.  Raises KmlError with code -4 where the mode is not available."""
+        a = 0.0 if alpha is None else float(alpha)
+        if alpha is not None and a == 0.0:
+            a = -1.0  # 0 means "the default" to the library; an explicit 0 is out of range
+        # an unknown name reaches the library as an unknown value, which answers KML_E_ARG
+        self._chk(lib().kml_set_algorithm(self._h, ALGORITHMS.get(algorithm, -1), a),
+                  f"kml_set_algorithm({algorithm!r}, {alpha!r})")
+
+    @property
+    def algorithm(self):
+        """(name, alpha): alpha is the min-sum normalisation factor as the library holds it (a float32 value)."""
+        a = C.c_double(0.0)
+        v = int(lib().kml_get_algorithm(self._h, C.byref(a)))
+        return {n: k for k, n in ALGORITHMS.items()}[v], a.value
 
     # ---- planner / host side
     def perm(self):

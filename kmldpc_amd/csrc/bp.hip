@@ -296,6 +296,11 @@ int kernel_variant() {
 }
 }  // namespace
 
+bool bp_generic_forced() {
+  const char *k = getenv("KML_BP_KERNEL");
+  return kernel_variant() == 1 || (k && k[0] == 'g');
+}
+
 bool bp_uses_lds(const DevCode &c) { return (long long)c.E * 16 + kRedBytes + c.N <= (long long)kLdsLimit; }
 
 const char *bp_profile_refusal(const DevCode &c, int iter_count) {
@@ -331,6 +336,23 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
   if (!queue) {
     if (err) *err = "dequeue counter missing";
     return hipErrorInvalidValue;
+  }
+  if (a.prec == 2) {  // the opt-in normalized min-sum mode: its kernel or an error, never another family
+    const char *why = nullptr;
+    if (a.cw_prof || a.prof) why = "the iteration profile is not available in the min-sum mode (a follow-up)";
+    if (a.syn) why = "the min-sum decoder has no syndrom_soft: syn must be NULL";
+    if (bp_generic_forced()) why = "the min-sum mode is not available with KML_BP_KERNEL=generic";
+    if (why) {
+      if (err) *err = why;
+      return hipErrorNotSupported;
+    }
+    hipError_t e = launch_bp_irregular_nms(c, a, s);
+    if (e == hipErrorNotSupported) {
+      if (err) *err = "the min-sum BP kernel does not take this code or launch";
+      return e;
+    }
+    if (family) *family = "bp_irregular_nms_kernel";
+    return e;
   }
   if (a.prec != 0) {  // the opt-in single-precision mode: its kernel or an error, never another family
     if (a.cw_prof || a.prof) {

@@ -175,6 +175,42 @@ int kml_set_precision(kml_ctx *c, int prec) {
 
 int kml_get_precision(const kml_ctx *c) { return c ? c->precision : KML_E_ARG; }
 
+int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
+  if (!c) return KML_E_ARG;
+  call_begin(c);
+  if (alg != KML_ALG_SPA && alg != KML_ALG_NMS)
+    return fail(c, KML_E_ARG, "kml_set_algorithm: unknown algorithm " + std::to_string(alg));
+  if (alg == KML_ALG_SPA) {  // always accepted, alpha ignored
+    c->algorithm = alg;
+    return KML_OK;
+  }
+  if (alpha == 0.0) alpha = 0.75;
+  if (!(alpha > 0.0 && alpha <= 1.0))  // NaN included
+    return fail(c, KML_E_ARG, "kml_set_algorithm: alpha must be 0 (the default 0.75) or in (0, 1]");
+  const float af = (float)alpha;
+  if (!(af > 0.0f))
+    return fail(c, KML_E_ARG, "kml_set_algorithm: alpha rounds to zero in single precision");
+  if (c->device < 0 || !c->stream)
+    return fail(c, KML_E_UNSUP, "kml_set_algorithm: a host-only context (device < 0) has no min-sum decoder");
+  if (c->precision != KML_PREC_F64)
+    return fail(c, KML_E_UNSUP, "kml_set_algorithm: the min-sum decoder is not available in the f32 precision");
+  if (kml::bp_generic_forced())
+    return fail(c, KML_E_UNSUP, "kml_set_algorithm: the min-sum decoder is not available with KML_BP_KERNEL=generic");
+  if (!kml::bp_irregular_nms_supported(c->dc))
+    return fail(c, KML_E_UNSUP,
+                "kml_set_algorithm: the min-sum decoder takes only the codes of bp_irregular_kernel (column degrees "
+                "<= 9, row degrees in [2, 10], messages in LDS); the context keeps its algorithm");
+  c->algorithm = alg;
+  c->nms_alpha = af;
+  return KML_OK;
+}
+
+int kml_get_algorithm(const kml_ctx *c, double *alpha) {
+  if (!c) return KML_E_ARG;
+  if (alpha) *alpha = (double)c->nms_alpha;
+  return c->algorithm;
+}
+
 int kml_dims(const kml_ctx *c, int32_t *d) {
   if (!c || !d) return KML_E_ARG;
   const kml::LdpcCode &L = c->code;
@@ -230,6 +266,8 @@ int kml_bp_decode(kml_ctx *c, const double *p0, int B, int iter_count, uint8_t *
   const bool ok = c && p0 && B >= 0 && iter_count >= 0;
   if (ok && B == 0) return KML_OK;
   TRY(gpu_begin(c, ok, "kml_bp_decode: bad argument"));
+  if (syn && c->algorithm == KML_ALG_NMS)
+    return fail(c, KML_E_UNSUP, "kml_bp_decode: the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
   const kml::LdpcCode &L = c->code;
   const double *d_p0;
   TRY(stage_in(c, c->w_p0, p0, (size_t)B * L.cc_len, flags, d_p0));
@@ -497,6 +535,9 @@ int kml_sim_decode_profile(kml_ctx *c, double snr, int blind, uint64_t *prof, in
   if (P < 1) return fail(c, KML_E_ARG, "kml_sim_decode_profile: max_iter must be >= 1");
   if (c->precision != KML_PREC_F64)
     return fail(c, KML_E_UNSUP, "kml_sim_decode_profile: the iteration profile is not available in the f32 mode");
+  if (c->algorithm != KML_ALG_SPA)
+    return fail(c, KML_E_UNSUP,
+                "kml_sim_decode_profile: the iteration profile is not available in the min-sum mode (KML_ALG_NMS)");
   if (c->rc.metric_soft)
     return fail(c, KML_E_UNSUP,
                 "kml_sim_decode_profile: the iteration profile is not available with the soft-syndrome metric "

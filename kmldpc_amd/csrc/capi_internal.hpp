@@ -71,6 +71,8 @@ struct kml_ctx {
   int device = 0;
   const char *bp_family = nullptr;  // kernel family of the last BP launch
   int precision = KML_PREC_F64;     // kml_set_precision: arithmetic of the final BP decodes
+  int algorithm = KML_ALG_SPA;      // kml_set_algorithm: decoder of the final BP decodes
+  float nms_alpha = 0.75f;          // ... and the min-sum normalisation factor
   hipStream_t stream = nullptr;
   hipStream_t cstream = nullptr;  // host-buffer frame uploads (kml_decode_frames' chunked path), made on first use
   kml::RunConfig rc;
@@ -197,7 +199,8 @@ int read_back(kml_ctx *c, const unsigned long long *cnt, uint64_t *counters, int
 // Launch BP over n entries with a fresh counter slot (*slot_out, when asked
 // for); reuse >= 0 accumulates into that (already zeroed) slot.
 // metric = true: a candidate-metric decode of the blind front end, which stays
-// fp64 in every mode (kml_set_precision changes the final decodes only).
+// fp64 sum-product in every mode (kml_set_precision and kml_set_algorithm
+// change the final decodes only).
 int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out = nullptr, int reuse = -1, bool metric = false);
 // The FAST demappers' defer list (kernels.hpp DemapDefer): at least `need`
 // entries (the candidate metric defers whole codewords: need = B).

@@ -288,6 +288,11 @@ int read_back(kml_ctx *c, const unsigned long long *cnt, uint64_t *counters, int
 
 int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric) {
   a.prec = metric ? KML_PREC_F64 : c->precision;
+  if (!metric && c->algorithm == KML_ALG_NMS) {  // (never with the f32 precision: kml_set_algorithm)
+    if (a.syn) return fail(c, KML_E_UNSUP, "the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
+    a.prec = 2;
+    a.nms_alpha = c->nms_alpha;
+  }
   int slot = reuse;
   if (reuse < 0) TRY(fresh_slot(c, slot));
   a.counters = slot_ptr(c, slot);

@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "layout.hpp"  // kIrrThreads, kIrrVnPairMax, kIrrCnPairMax
@@ -57,6 +58,10 @@ enum {
 struct BpLaunch {
   int B = 0;
   int iter_count = 0, max_iter = 0;
+  // prec = 2 (below): the normalisation factor of the min-sum CN phase, in
+  // (0, 1].  It sits in what was the padding ahead of p0: no field moves and
+  // the struct keeps its size, so the existing kernels' code is unchanged.
+  float nms_alpha = 0.75f;
   const double *p0 = nullptr;
   long long p0_stride = 0;       // doubles between codewords
   const int32_t *p0_sel = nullptr;  // optional per-codeword candidate: p0 += sel*p0_sel_stride
@@ -100,7 +105,9 @@ struct BpLaunch {
   int sym_bits = 0;
   // 0: the bit-exact fp64 kernels; 1: the single-precision kernel
   // (bp_regular_f32.hip, PEG2304-class codes only; launch_bp fails for any
-  // other code, there is no fallback in either direction)
+  // other code, there is no fallback in either direction); 2: the normalized
+  // min-sum kernel (bp_irregular_nms.hip, the codes of bp_irregular.hip only,
+  // nms_alpha above; the same rule)
   int prec = 0;
   // Iteration profile (bp_regular.hip / bp_irregular.hip only, SYN = false,
   // ref_bits set, 1 <= iter_count <= kBpProfMaxIter): when either is set the
@@ -114,6 +121,10 @@ struct BpLaunch {
   long long cw_prof_stride = 0;
   unsigned long long *prof = nullptr;
 };
+// The kernels take BpLaunch by value, so its layout is part of their code; the
+// arguments that follow it (queue, fast_allowed, ...) sit behind its size.
+static_assert(sizeof(BpLaunch) == 280 && offsetof(BpLaunch, p0) == 16 && offsetof(BpLaunch, prof) == 272,
+              "BpLaunch layout changed: every BP kernel's kernarg offsets move with it");
 
 constexpr int kBpProfMaxIter = 64;  // budgets of a profile launch (static LDS: perr + wprof, 1792 B)
 
@@ -133,6 +144,12 @@ bool bp_regular_fuses_demap(const DevCode &c, int bits);
 hipError_t launch_bp_regular_f32(const DevCode &c, const BpLaunch &a, hipStream_t s);
 bool bp_regular_f32_supported(const DevCode &c);
 hipError_t launch_bp_irregular(const DevCode &c, const BpLaunch &a, hipStream_t s);
+// The normalized min-sum sibling (BpLaunch::prec = 2) and whether this code
+// takes it: the codes of launch_bp_irregular whose min-sum state fits in LDS.
+hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, hipStream_t s);
+bool bp_irregular_nms_supported(const DevCode &c);
+// KML_BP_KERNEL=generic (read now, and as the dispatch first read it).
+bool bp_generic_forced();
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of
 // workgroups on one XCD share a codeword.  0 groups = not applicable.
 int bp_coop_groups(const DevCode &c);

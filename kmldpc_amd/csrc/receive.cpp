@@ -177,6 +177,11 @@ int soft_receive(kml_ctx *c, const RecvIO &io, double var, int B, const double2 
 int receive(kml_ctx *c, const RecvIO &io, double snr, int B, int &bp_slot) {
   double var, sigma, ns;
   kml::channel_constants(snr, var, sigma, ns);
+  // the soft walk reads the final decodes' syndrom_soft, which min-sum does not
+  // have: refused before k-means or anything else is launched
+  if (c->algorithm == KML_ALG_NMS && c->rc.metric_soft && !(io.true_h && !io.histogram))
+    return fail(c, KML_E_UNSUP,
+                "the soft-syndrome metric (metric_type = 1) is not available in the min-sum mode (KML_ALG_NMS)");
   if (io.true_h && !io.histogram)  // known channel: no candidates, no metric
     return demap_then_bp(c, final_launch(c, io, B), io.y, io.true_h, 1, nullptr, var, bp_slot);
   // candidate channel estimates: the caller's, the true h (histogram on the

@@ -17,7 +17,10 @@
 // GPU round, default 32768), KML_SEED (frame seed, default 0 like
 // CLCRandNum::SetSeed(0) in kmldpc.cpp:22), KML_PRECISION (f64 or f32, also
 // `--precision f64|f32` on the command line: the BP decode arithmetic,
-// kml_set_precision; an f32 run states the mode in its first line).
+// kml_set_precision; an f32 run states the mode in its first line),
+// KML_ALGORITHM (spa, nms or nms:alpha, also `--algorithm spa|nms[:alpha]`: the
+// decoder of the final BP decodes, kml_set_algorithm; an nms run states the
+// mode in its first line).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -95,12 +98,17 @@ int main(int argc, char **argv) {
     g_log = fopen(name.c_str(), "w");
   }
   std::string cfg = "config.toml", prec = getenv("KML_PRECISION") ? getenv("KML_PRECISION") : "f64";
+  std::string alg = getenv("KML_ALGORITHM") ? getenv("KML_ALGORITHM") : "spa";
   for (int i = 1; i < argc; i++) {
     const std::string arg = argv[i];
     if (arg == "--precision" && i + 1 < argc)
       prec = argv[++i];
     else if (arg.rfind("--precision=", 0) == 0)
       prec = arg.substr(12);
+    else if (arg == "--algorithm" && i + 1 < argc)
+      alg = argv[++i];
+    else if (arg.rfind("--algorithm=", 0) == 0)
+      alg = arg.substr(12);
     else
       cfg = arg;
   }
@@ -108,7 +116,23 @@ int main(int argc, char **argv) {
     error("--precision / KML_PRECISION must be f64 or f32");
     return 255;
   }
+  // spa | nms | nms:alpha (alpha = 0: the library's default, 0.75)
+  double alpha = 0.0;
+  bool alg_ok = alg == "spa" || alg == "nms";
+  if (alg.rfind("nms:", 0) == 0 && alg.size() > 4) {
+    char *end = nullptr;
+    alpha = strtod(alg.c_str() + 4, &end);
+    alg_ok = *end == '\0' && alpha > 0.0 && alpha <= 1.0;
+    alg = "nms";
+  }
+  if (!alg_ok) {
+    error("--algorithm / KML_ALGORITHM must be spa, nms or nms:alpha with 0 < alpha <= 1");
+    return 255;
+  }
   if (prec == "f32") info("BP decode precision: f32 (single precision, not bit-exact with the reference)");
+  if (alg == "nms")
+    info(fmt("BP decode algorithm: nms (normalized min-sum, alpha = %g; not the reference's decoder)",
+             alpha > 0.0 ? (double)(float)alpha : 0.75));
   info("Start simulation");
   {
     FILE *f = fopen(cfg.c_str(), "rb");
@@ -129,6 +153,11 @@ int main(int argc, char **argv) {
     return 255;  // the reference exits with -1 on setup errors
   }
   if (prec == "f32" && kml_set_precision(ctx, KML_PREC_F32) != KML_OK) {
+    error(kml_last_error(ctx));
+    kml_destroy(ctx);
+    return 255;
+  }
+  if (alg == "nms" && kml_set_algorithm(ctx, KML_ALG_NMS, alpha) != KML_OK) {
     error(kml_last_error(ctx));
     kml_destroy(ctx);
     return 255;

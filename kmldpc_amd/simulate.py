@@ -76,10 +76,10 @@ class Simulator:
     """Simulator (include/simulator.h): constructed from config.toml, Simulate() runs the sweep."""
 
     def __init__(self, config, data_dir=None, device=0, batch=32768, seed=0, dist=None, log=None, comm_backend="nccl",
-                 precision="f64"):
+                 precision="f64", algorithm="spa"):
         self.log = log or Logger(enabled=(dist.get_rank() if dist else 0) == 0)
         self.ctx = Context(config, data_dir=data_dir or os.path.dirname(os.path.abspath(config)), device=device,
-                           precision=precision)
+                           precision=precision, algorithm=algorithm)
         self.rc = self.ctx.run_config()
         self.batch = int(batch)
         self.seed = int(seed)
@@ -147,6 +147,10 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["f64", "f32"], default=os.environ.get("KML_PRECISION", "f64"),
                     help="BP decode arithmetic: f64 (default, bit-exact with the reference) or f32 (opt-in, "
                          "PEG2304-class codes only, not bit-exact)")
+    ap.add_argument("--algorithm", default=os.environ.get("KML_ALGORITHM", "spa"), metavar="spa|nms[:alpha]",
+                    help="decoder of the final BP decodes: spa (default, the reference's sum-product, bit-exact) or "
+                         "nms (opt-in normalized min-sum, alpha in (0, 1], default 0.75; the codes of "
+                         "bp_irregular_kernel only, e.g. 5G BG2; not the reference's decoder)")
     ap.add_argument("--force-dist", action="store_true", default=os.environ.get("KML_FORCE_DIST", "") == "1",
                     help="build the process group (and run its all-reduces) even when WORLD_SIZE is 1, "
                          "e.g. a 1-rank RCCL group under torchrun --nproc-per-node 1")
@@ -158,6 +162,16 @@ def main(argv=None):
     log = Logger(enabled=rank == 0)
     if args.precision != "f64":  # the first line of an f32 run states the mode; every other line keeps its format
         log.info(f"BP decode precision: {args.precision} (single precision, not bit-exact with the reference)")
+    alg_name, alg_colon, alg_alpha = args.algorithm.partition(":")
+    try:  # (a colon with nothing behind it is an error here as in kmldpc_sim)
+        alg_ok = alg_name in ("spa", "nms") and (not alg_colon or (alg_name == "nms" and 0.0 < float(alg_alpha) <= 1.0))
+    except ValueError:
+        alg_ok = False
+    if not alg_ok:
+        ap.error("--algorithm / KML_ALGORITHM must be spa, nms or nms:alpha with 0 < alpha <= 1")
+    if alg_name == "nms":  # the first line of an nms run states the mode too
+        log.info(f"BP decode algorithm: nms (normalized min-sum, alpha = {float(alg_alpha or 0.75):g}; "
+                 "not the reference's decoder)")
     log.info("Start simulation")
     if not os.path.exists(args.config):
         log.error("Encouter error while opening config.toml")
@@ -175,7 +189,7 @@ def main(argv=None):
             local = local % max(torch.cuda.device_count(), 1)
         dist = dist_mod
     sim = Simulator(args.config, device=local, batch=args.batch, seed=args.seed, dist=dist, log=log,
-                    comm_backend=args.dist_backend, precision=args.precision)
+                    comm_backend=args.dist_backend, precision=args.precision, algorithm=args.algorithm)
     sim.Simulate()
     sim.ctx.close()
     if dist is not None:
