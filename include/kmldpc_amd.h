@@ -182,6 +182,57 @@ enum { KML_ALG_SPA = 0, KML_ALG_NMS = 1 };
 int kml_set_algorithm(kml_ctx *ctx, int alg, double alpha);
 int kml_get_algorithm(const kml_ctx *ctx, double *alpha /* may be NULL */);
 
+/* Row schedule of the min-sum decodes, per context: a third axis beside
+ * precision and algorithm.  KML_SCHED_FLOODING (the default) is the decoder
+ * above: one VN phase over all columns, then one CN phase over all rows.
+ * KML_SCHED_LAYERED is the schedule a 5G receiver runs
+ * ("bp_irregular_lnms_kernel" in kml_bp_kernel): one posterior per column, the
+ * rows taken in index order, each reading what the rows before it left.  It
+ * reaches the flooding schedule's error rate in about half the iterations.
+ * Its arithmetic is tests/bp_lnms_model.py's, which the kernel equals bit for
+ * bit (uu_hat, ret, cc_hat).  Priors, alpha, the +-256 clamp, the tie rule and
+ * the number format are the flooding decoder's (above):
+ *   state     T[v] = L[v], one posterior per column; c2v[e] = +0, one message
+ *             per edge in row-major order;
+ *   loop      hard = (T > 0 ? 0 : 1); it = 0; then, repeatedly: when every
+ *             check row of hard has even parity, stop (converged); when
+ *             it == iter_count, stop; otherwise one sweep, it += 1,
+ *             hard = (T > 0 ? 0 : 1);
+ *   sweep     rows r = 0 .. M-1 in index order; for each edge j of r (column
+ *             v_j): m_j = clamp(T[v_j] - c2v_j, -256.0f, 256.0f); then
+ *             a_j = min over i != j of |m_i|, s_j = XOR over i != j of the
+ *             IEEE sign bits of m_i (-0 counts as negative),
+ *             c2v_j = RN(alpha * a_j) with its sign bit set to s_j, and
+ *             T[v_j] = m_j + c2v_j;
+ *   result    ret = it + (it < max_iter); uu_hat / cc_hat are hard;
+ *             iter_count = 0 leaves them as passed.
+ * A budget of k uses all k sweeps: the decisions are those of the posteriors
+ * the k-th sweep left.  (The flooding schedule never reads its last CN phase;
+ * the difference is deliberate.)  Counters: `it` CN phases, it + 1 (converged)
+ * or it VN phases; CNT_REDONE stays 0.
+ * A layer is a maximal run of consecutive rows with pairwise disjoint columns,
+ * found greedily in row order: a row that shares a column with the open layer
+ * closes it and opens the next.  Its rows touch disjoint T and c2v entries, so
+ * the kernel works on them in parallel and still computes the serial sweep:
+ * layers are a matter of speed, not of the arithmetic.  kml_code_layers returns
+ * the number of layers nl and writes min(cap, nl + 1) entries of layer_ptr
+ * (layer l = rows [layer_ptr[l], layer_ptr[l + 1])); it works on a host-only
+ * context and answers KML_E_UNSUP for a code the min-sum mode does not take
+ * (5G BG2 K960: 12 layers of 96 rows).
+ * The schedule belongs to the min-sum mode.  KML_SCHED_FLOODING is always
+ * accepted.  KML_SCHED_LAYERED returns KML_E_UNSUP, and the context keeps its
+ * schedule, on a host-only context, on a context whose algorithm is not
+ * KML_ALG_NMS, and with KML_BP_KERNEL=generic; an unknown value returns
+ * KML_E_ARG.  kml_set_algorithm(KML_ALG_SPA) returns the schedule to flooding;
+ * kml_set_algorithm(KML_ALG_NMS, alpha) keeps it.  The scope and the refusals
+ * (syn, the soft-syndrome metric, kml_sim_decode_profile) are those of
+ * kml_set_algorithm.  There is no fallback to another kernel. */
+#define KML_SCHED_FLOODING 0
+#define KML_SCHED_LAYERED 1
+int kml_set_schedule(kml_ctx *ctx, int sched);
+int kml_get_schedule(const kml_ctx *ctx);
+int kml_code_layers(const kml_ctx *ctx, int32_t *layer_ptr, int cap);
+
 int kml_dims(const kml_ctx *ctx, int32_t *dims /* [KML_DIM_COUNT] */);
 /* Host-side code plan, for inspection and parity tests. */
 int kml_code_perm(const kml_ctx *ctx, int32_t *perm /* [Ncol] */);

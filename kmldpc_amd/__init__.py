@@ -32,6 +32,7 @@ KML_DEVICE_PTRS = 1
 KML_HISTOGRAM = 2
 PRECISIONS = {"f64": 0, "f32": 1}  # KML_PREC_F64, KML_PREC_F32
 ALGORITHMS = {"spa": 0, "nms": 1}  # KML_ALG_SPA, KML_ALG_NMS
+SCHEDULES = {"flooding": 0, "layered": 1}  # KML_SCHED_FLOODING, KML_SCHED_LAYERED
 DIM_NAMES = ["M", "Ncol", "K", "cc_len", "Z", "E", "chk", "max_iter", "bits", "Kc", "S", "bp_lds", "part_group"]
 
 
@@ -82,6 +83,9 @@ def lib():
         "kml_get_precision": (I, [P]),
         "kml_set_algorithm": (I, [P, I, D]),
         "kml_get_algorithm": (I, [P, P]),
+        "kml_set_schedule": (I, [P, I]),
+        "kml_get_schedule": (I, [P]),
+        "kml_code_layers": (I, [P, P, I]),
         "kml_create": (I, [C.c_char_p, C.c_char_p, I, PP]),
         "kml_create_explicit": (I, [C.c_char_p, C.c_char_p, I, I, I, I, I, I, PP]),
         "kml_destroy": (None, [P]),
@@ -171,7 +175,8 @@ class Context:
     """One code + modem on one GPU (device < 0: host-only planner context)."""
 
     def __init__(self, config=None, data_dir=None, device=0, *, matrix_file=None, modem_file=None, is5g=False,
-                 active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64", algorithm="spa"):
+                 active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64", algorithm="spa",
+                 schedule="flooding"):
         L = lib()
         h = C.c_void_p()
         if config is not None:
@@ -205,6 +210,12 @@ class Context:
         if algorithm != "spa":
             try:
                 self.set_algorithm(*_parse_algorithm(algorithm))
+            except Exception:
+                self.close()
+                raise
+        if schedule != "flooding":
+            try:
+                self.set_schedule(schedule)
             except Exception:
                 self.close()
                 raise
@@ -263,6 +274,31 @@ class Context:
         a = C.c_double(0.0)
         v = int(lib().kml_get_algorithm(self._h, C.byref(a)))
         return {n: k for k, n in ALGORITHMS.items()}[v], a.value
+
+    # ---- row schedule of the min-sum decodes (kml_set_schedule)
+    def set_schedule(self, schedule):
+        """"flooding" (default, always accepted) or "layered" (opt-in, the min-sum mode only: rows in index
+        order on one posterior per column, about half the iterations for the same error rate; its arithmetic is
+        tests/bp_lnms_model.py's bit for bit).  Raises KmlError with code -4 where it is not available."""
+        # an unknown name reaches the library as an unknown value, which answers KML_E_ARG
+        self._chk(lib().kml_set_schedule(self._h, SCHEDULES.get(schedule, -1)), f"kml_set_schedule({schedule!r})")
+
+    @property
+    def schedule(self):
+        v = int(lib().kml_get_schedule(self._h))
+        return {n: k for k, n in SCHEDULES.items()}[v]
+
+    def layers(self):
+        """layer_ptr[nl + 1] of the layered schedule (kml_code_layers): layer l = rows [layer_ptr[l], layer_ptr[l + 1])."""
+        nl = self._chk_count(lib().kml_code_layers(self._h, None, 0), "kml_code_layers")
+        lp = np.zeros(nl + 1, np.int32)
+        self._chk_count(lib().kml_code_layers(self._h, _p(lp), nl + 1), "kml_code_layers")
+        return lp
+
+    def _chk_count(self, r, what):
+        if r < 0:
+            self._chk(r, what)
+        return int(r)
 
     # ---- planner / host side
     def perm(self):

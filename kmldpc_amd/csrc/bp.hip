@@ -326,7 +326,8 @@ long long bp_gslots_needed(const DevCode &c) {
   return (long long)device_cus() * 4 * c.E;  // up to 4 resident workgroups per CU
 }
 
-hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family) {
+hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family,
+                     const LnmsPlanDev *lnms) {
   if (a.B <= 0) return hipSuccess;
   if (a.iter_count < 0) {
     if (err) *err = "iter_count must be >= 0";
@@ -337,7 +338,8 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
     if (err) *err = "dequeue counter missing";
     return hipErrorInvalidValue;
   }
-  if (a.prec == 2) {  // the opt-in normalized min-sum mode: its kernel or an error, never another family
+  if (a.prec == 2 || a.prec == 3) {  // the opt-in normalized min-sum mode: its kernel or an error, never another family
+    const bool layered = a.prec == 3;  // ... in the layered schedule: bp_irregular_lnms.hip, by the same rule
     const char *why = nullptr;
     if (a.cw_prof || a.prof) why = "the iteration profile is not available in the min-sum mode (a follow-up)";
     if (a.syn) why = "the min-sum decoder has no syndrom_soft: syn must be NULL";
@@ -346,12 +348,18 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
       if (err) *err = why;
       return hipErrorNotSupported;
     }
-    hipError_t e = launch_bp_irregular_nms(c, a, s);
+    if (layered && !lnms) {
+      if (err) *err = "the layered min-sum schedule needs the code's layer plan";
+      return hipErrorNotSupported;
+    }
+    hipError_t e = layered ? launch_bp_irregular_lnms(c, a, *lnms, s) : launch_bp_irregular_nms(c, a, s);
     if (e == hipErrorNotSupported) {
-      if (err) *err = "the min-sum BP kernel does not take this code or launch";
+      if (err)
+        *err = layered ? "the layered min-sum BP kernel does not take this code or launch"
+                       : "the min-sum BP kernel does not take this code or launch";
       return e;
     }
-    if (family) *family = "bp_irregular_nms_kernel";
+    if (family) *family = layered ? "bp_irregular_lnms_kernel" : "bp_irregular_nms_kernel";
     return e;
   }
   if (a.prec != 0) {  // the opt-in single-precision mode: its kernel or an error, never another family

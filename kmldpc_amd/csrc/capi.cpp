@@ -180,8 +180,9 @@ int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
   call_begin(c);
   if (alg != KML_ALG_SPA && alg != KML_ALG_NMS)
     return fail(c, KML_E_ARG, "kml_set_algorithm: unknown algorithm " + std::to_string(alg));
-  if (alg == KML_ALG_SPA) {  // always accepted, alpha ignored
+  if (alg == KML_ALG_SPA) {  // always accepted, alpha ignored; the schedule belongs to the min-sum mode
     c->algorithm = alg;
+    c->schedule = KML_SCHED_FLOODING;
     return KML_OK;
   }
   if (alpha == 0.0) alpha = 0.75;
@@ -209,6 +210,40 @@ int kml_get_algorithm(const kml_ctx *c, double *alpha) {
   if (!c) return KML_E_ARG;
   if (alpha) *alpha = (double)c->nms_alpha;
   return c->algorithm;
+}
+
+int kml_set_schedule(kml_ctx *c, int sched) {
+  if (!c) return KML_E_ARG;
+  call_begin(c);
+  if (sched != KML_SCHED_FLOODING && sched != KML_SCHED_LAYERED)
+    return fail(c, KML_E_ARG, "kml_set_schedule: unknown schedule " + std::to_string(sched));
+  if (sched == KML_SCHED_FLOODING) {  // always accepted
+    c->schedule = sched;
+    return KML_OK;
+  }
+  if (c->device < 0 || !c->stream)
+    return fail(c, KML_E_UNSUP, "kml_set_schedule: a host-only context (device < 0) has no min-sum decoder");
+  if (kml::bp_generic_forced())
+    return fail(c, KML_E_UNSUP, "kml_set_schedule: the layered schedule is not available with KML_BP_KERNEL=generic");
+  if (c->algorithm != KML_ALG_NMS)
+    return fail(c, KML_E_UNSUP,
+                "kml_set_schedule: the layered schedule belongs to the min-sum mode (kml_set_algorithm(KML_ALG_NMS) "
+                "first); the context keeps its schedule");
+  if (!c->lnms_dev.pass)  // (never in the min-sum mode: the plan is made for every code that mode accepts)
+    return fail(c, KML_E_UNSUP, "kml_set_schedule: the code has no layer plan");
+  c->schedule = sched;
+  return KML_OK;
+}
+
+int kml_get_schedule(const kml_ctx *c) { return c ? c->schedule : KML_E_ARG; }
+
+int kml_code_layers(const kml_ctx *c, int32_t *layer_ptr, int cap) {
+  if (!c || cap < 0 || (cap > 0 && !layer_ptr)) return KML_E_ARG;
+  const std::vector<int32_t> &lp = c->layered.layer_ptr;
+  if (lp.empty()) return KML_E_UNSUP;
+  const int n = std::min<int>(cap, (int)lp.size());
+  for (int i = 0; i < n; i++) layer_ptr[i] = lp[i];
+  return (int)lp.size() - 1;
 }
 
 int kml_dims(const kml_ctx *c, int32_t *d) {

@@ -73,6 +73,9 @@ struct kml_ctx {
   int precision = KML_PREC_F64;     // kml_set_precision: arithmetic of the final BP decodes
   int algorithm = KML_ALG_SPA;      // kml_set_algorithm: decoder of the final BP decodes
   float nms_alpha = 0.75f;          // ... and the min-sum normalisation factor
+  int schedule = KML_SCHED_FLOODING;  // kml_set_schedule: row schedule of the min-sum decodes
+  kml::LayeredPlan layered;         // its layers (empty: the code has none, kml_code_layers says KML_E_UNSUP)
+  kml::LnmsPlanDev lnms_dev;        // ... and the device copy of the passes (d_lnms)
   hipStream_t stream = nullptr;
   hipStream_t cstream = nullptr;  // host-buffer frame uploads (kml_decode_frames' chunked path), made on first use
   kml::RunConfig rc;
@@ -82,7 +85,7 @@ struct kml_ctx {
   double rot[8];
   using DBuf = kml_host::DBuf;
   // resident constants
-  DBuf d_graph, d_cons;
+  DBuf d_graph, d_cons, d_lnms;
   // algorithmic fp64 flops per executed VN / CN phase ("Roofline")
   double vn_flops = 0, cn_flops = 0;
   DBuf d_arena;  // kArenaSlots x CNT_N counters

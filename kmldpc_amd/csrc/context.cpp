@@ -4,6 +4,7 @@
 // the BP / demap / k-means launches every path above goes through.
 #include <cstdio>
 
+#include "bp_launch.hpp"
 #include "capi_internal.hpp"
 
 namespace kml_host {
@@ -190,7 +191,43 @@ int upload_code(kml_ctx *c) {
     HIPCHK(c, hipMemset(c->d_gsync.p, 0, kml::bp_coop_sync_bytes(c->coop_groups)), "memset(gsync)");
     HIPCHK(c, c->d_gcch.ensure((size_t)c->coop_groups * L.N), "hipMalloc(gcch)");
   }
+  // layer plan of the layered min-sum kernel (layout.hpp LayeredPlan), in an
+  // allocation of its own: it reaches the kernel beside DevCode, not in it
+  if (kml::bp_irregular_nms_supported(d)) {
+    kml::plan_layered(L, c->layered);
+    const size_t bytes = c->layered.pass.size() * sizeof(int32_t);
+    HIPCHK(c, c->d_lnms.ensure(bytes), "hipMalloc(layer plan)");
+    HIPCHK(c, hipMemcpy(c->d_lnms.p, c->layered.pass.data(), bytes, hipMemcpyHostToDevice), "upload layer plan");
+    c->lnms_dev.pass = c->d_lnms.as<int32_t>();
+    c->lnms_dev.npass = (int)c->layered.pass.size();
+  }
   return KML_OK;
+}
+
+// The layer plan of a host-only context: bp_irregular_nms_supported restated
+// on the host plan (no DevCode without a GPU), so kml_code_layers answers for
+// the same codes with and without one.
+void plan_layers_host(kml_ctx *c) {
+  const kml::LdpcCode &L = c->code;
+  bool regular = true, irr_ok = true;
+  for (int j = 0; j < L.N; j++) {
+    const int dv = L.col_ptr[j + 1] - L.col_ptr[j];
+    regular &= dv == L.dv_max;
+    irr_ok &= dv >= 1 && dv <= 9;
+  }
+  for (int i = 0; i < L.M; i++) {
+    const int dc = L.row_ptr[i + 1] - L.row_ptr[i];
+    regular &= dc == L.dc_max;
+    irr_ok &= dc >= 2 && dc <= 10;
+  }
+  kml::IrregularPlan irr;
+  if (regular || !irr_ok || !kml::plan_irregular(L, kml::kIrrThreads, kml::kIrrVnPairMax, kml::kIrrCnPairMax, irr))
+    return;
+  const size_t fixed = (size_t)L.E * 2 + 16 + (size_t)L.N;  // the slot table, the tallies, the decision bytes
+  const size_t sibling = (size_t)irr.n_slots * 16 + (size_t)L.cc_len * 8 + fixed;
+  const size_t nms = (size_t)irr.n_slots * 8 + (size_t)L.cc_len * 4 + fixed;
+  if (irr.n_slots > 16383 || sibling > kml::kLdsLimit || nms > kml::kLdsLimit) return;
+  kml::plan_layered(L, c->layered);
 }
 
 // FP64 work of one VN / CN phase of the exact algorithm: per column of degree
@@ -218,7 +255,10 @@ int finish_create(kml_ctx *c) {
   if (c->modem.bits != 1 && c->modem.bits != 2 && c->modem.bits != 3 && c->modem.bits != 4 && c->modem.bits != 6)
     return fail(c, KML_E_UNSUP, "bits per symbol must be 1, 2, 3, 4 or 6");
   kml::rotation_factors(c->rot);
-  if (c->device < 0) return KML_OK;  // host-only context: planner + encoder, no GPU
+  if (c->device < 0) {  // host-only context: planner + encoder, no GPU
+    plan_layers_host(c);
+    return KML_OK;
+  }
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
   return upload_code(c);
@@ -290,7 +330,7 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric) {
   a.prec = metric ? KML_PREC_F64 : c->precision;
   if (!metric && c->algorithm == KML_ALG_NMS) {  // (never with the f32 precision: kml_set_algorithm)
     if (a.syn) return fail(c, KML_E_UNSUP, "the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
-    a.prec = 2;
+    a.prec = c->schedule == KML_SCHED_LAYERED ? 3 : 2;
     a.nms_alpha = c->nms_alpha;
   }
   int slot = reuse;
@@ -314,7 +354,7 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric) {
   }
   Timer t(c, "bp", slot, (double)a.B * 8.0 * c->code.cc_len);
   const char *msg = nullptr;
-  hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family);
+  hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family, &c->lnms_dev);
   t.stop();
   if (e != hipSuccess) return msg ? fail(c, KML_E_UNSUP, msg) : hip_fail(c, e, "bp launch");
   if (c->inject_abort >= 0 && c->coop_groups > 0 && c->inject_abort-- == 0)  // as if a group barrier timed out

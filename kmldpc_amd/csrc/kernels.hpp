@@ -107,7 +107,8 @@ struct BpLaunch {
   // (bp_regular_f32.hip, PEG2304-class codes only; launch_bp fails for any
   // other code, there is no fallback in either direction); 2: the normalized
   // min-sum kernel (bp_irregular_nms.hip, the codes of bp_irregular.hip only,
-  // nms_alpha above; the same rule)
+  // nms_alpha above; the same rule); 3: its layered schedule
+  // (bp_irregular_lnms.hip, the same codes, nms_alpha, launch_bp's lnms plan)
   int prec = 0;
   // Iteration profile (bp_regular.hip / bp_irregular.hip only, SYN = false,
   // ref_bits set, 1 <= iter_count <= kBpProfMaxIter): when either is set the
@@ -148,6 +149,15 @@ hipError_t launch_bp_irregular(const DevCode &c, const BpLaunch &a, hipStream_t 
 // takes it: the codes of launch_bp_irregular whose min-sum state fits in LDS.
 hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, hipStream_t s);
 bool bp_irregular_nms_supported(const DevCode &c);
+// The layered min-sum sibling (BpLaunch::prec = 3, bp_irregular_lnms.hip): the
+// codes of launch_bp_irregular_nms.  Its layer plan (layout.hpp LayeredPlan)
+// travels as a kernel argument of its own: DevCode and BpLaunch are part of the
+// existing kernels' code and neither grows.
+struct LnmsPlanDev {
+  const int32_t *pass = nullptr;  // LayeredPlan::pass, device copy
+  int npass = 0;
+};
+hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, hipStream_t s);
 // KML_BP_KERNEL=generic (read now, and as the dispatch first read it).
 bool bp_generic_forced();
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of
@@ -170,8 +180,9 @@ hipError_t bp_coop_raise_abort(const BpLaunch &a, int groups, hipStream_t s);
 // not apply (host-side; decides whether upload_code builds the LDS plan).
 int bp_regular_threads(int N, int M, int E, int dv_max, int dc_max, int regular);
 // family (optional) receives the name of the kernel that was launched.
+// lnms: the layer plan, read by prec = 3 only (which fails without one).
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err,
-                     const char **family = nullptr);
+                     const char **family = nullptr, const LnmsPlanDev *lnms = nullptr);
 // Workspace the BP launcher needs in global-slot mode (double2 elements).
 long long bp_gslots_needed(const DevCode &c);
 bool bp_uses_lds(const DevCode &c);

@@ -807,4 +807,30 @@ bool plan_irregular(const LdpcCode &L, int T, int vn_pair_max, int cn_pair_max, 
   return place_slot_blocks(L, T, out);
 }
 
+// ---------------------------------------- LayeredPlan (bp_irregular_lnms)
+void plan_layered(const LdpcCode &L, LayeredPlan &out) {
+  out.layer_ptr.assign(1, 0);
+  out.pass.clear();
+  std::vector<int32_t> open_at(L.N, -1);  // column -> first row of the layer that last touched it
+  int first = 0;
+  auto close = [&](int end) {  // the layer [first, end) in passes
+    for (int r = first; r < end; r += kLayRowsPerPass) {
+      const int n = std::min(kLayRowsPerPass, end - r);
+      out.pass.push_back(r | n << 16 | (r + n == end ? 1 : 0) << 24);
+    }
+  };
+  for (int r = 0; r < L.M; ++r) {
+    bool shared = false;
+    for (int e = L.row_ptr[r]; e < L.row_ptr[r + 1]; ++e) shared |= open_at[L.row_col[e]] == first;
+    if (shared && r > first) {
+      close(r);
+      out.layer_ptr.push_back(r);
+      first = r;
+    }
+    for (int e = L.row_ptr[r]; e < L.row_ptr[r + 1]; ++e) open_at[L.row_col[e]] = first;
+  }
+  close(L.M);
+  out.layer_ptr.push_back(L.M);
+}
+
 }  // namespace kml

@@ -6,6 +6,8 @@
 //                                       and columns, and the cut-edge exchange;
 //   IrregularPlan  (bp_irregular.hip)   which wave and round runs which
 //                                       columns / rows, and the slot blocks.
+// A fourth, LayeredPlan (bp_irregular_lnms.hip), is the row layers of the
+// layered min-sum schedule and the passes the kernel cuts them into.
 // A plan changes nothing in the arithmetic: any valid plan gives the same
 // decoder output, it only moves work between lanes, so it decides speed (LDS
 // bank conflicts, mailbox traffic, SIMD balance) and nothing else.
@@ -128,6 +130,29 @@ struct IrregularPlan {
 
 // False when the code's degree groups do not fit three rounds of T lanes.
 bool plan_irregular(const LdpcCode &L, int T, int vn_pair_max, int cn_pair_max, IrregularPlan &out);
+
+// ---------------------------------------- LayeredPlan (bp_irregular_lnms)
+// Layer plan of the layered min-sum kernel (bp_irregular_lnms.hip).  A layer
+// is a maximal run of consecutive rows with pairwise disjoint columns, found
+// greedily in row order: a row that shares a column with the open layer closes
+// it and opens the next (kml_code_layers; 5G BG2 K960: 12 layers of 96 rows).
+// The rows of a layer touch disjoint posteriors and messages, so the kernel
+// works on them in parallel and still computes the serial row-by-row sweep.
+// A workgroup takes kLayRowsPerPass rows at a time (kLayLanesPerRow lanes per
+// row); a layer is cut into passes of at most that many rows, and only a
+// layer's last pass ends with a barrier.  Not one of the three digested plans
+// above: the layers are pinned through kml_code_layers instead.
+constexpr int kLayLanesPerRow = 8;                              // lanes that share a row (<= 2 edges each)
+constexpr int kLayRowsPerPass = kIrrThreads / kLayLanesPerRow;  // 96
+
+struct LayeredPlan {
+  std::vector<int32_t> layer_ptr;  // [nl + 1]: layer l = rows [layer_ptr[l], layer_ptr[l + 1])
+  // one word per pass, in sweep order: first row | rows << 16 | (last pass of its layer) << 24
+  std::vector<int32_t> pass;
+};
+
+// Any code (rows of any degree); the kernel's own limits are the launcher's.
+void plan_layered(const LdpcCode &L, LayeredPlan &out);
 
 }  // namespace kml
 

@@ -20,7 +20,10 @@
 // kml_set_precision; an f32 run states the mode in its first line),
 // KML_ALGORITHM (spa, nms or nms:alpha, also `--algorithm spa|nms[:alpha]`: the
 // decoder of the final BP decodes, kml_set_algorithm; an nms run states the
-// mode in its first line).
+// mode in its first line), KML_SCHEDULE (flooding or layered, also
+// `--schedule flooding|layered`: the row schedule of the min-sum decodes,
+// kml_set_schedule; layered needs nms and states itself in the line after the
+// algorithm's).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -99,6 +102,7 @@ int main(int argc, char **argv) {
   }
   std::string cfg = "config.toml", prec = getenv("KML_PRECISION") ? getenv("KML_PRECISION") : "f64";
   std::string alg = getenv("KML_ALGORITHM") ? getenv("KML_ALGORITHM") : "spa";
+  std::string sched = getenv("KML_SCHEDULE") ? getenv("KML_SCHEDULE") : "flooding";
   for (int i = 1; i < argc; i++) {
     const std::string arg = argv[i];
     if (arg == "--precision" && i + 1 < argc)
@@ -109,6 +113,10 @@ int main(int argc, char **argv) {
       alg = argv[++i];
     else if (arg.rfind("--algorithm=", 0) == 0)
       alg = arg.substr(12);
+    else if (arg == "--schedule" && i + 1 < argc)
+      sched = argv[++i];
+    else if (arg.rfind("--schedule=", 0) == 0)
+      sched = arg.substr(11);
     else
       cfg = arg;
   }
@@ -129,10 +137,19 @@ int main(int argc, char **argv) {
     error("--algorithm / KML_ALGORITHM must be spa, nms or nms:alpha with 0 < alpha <= 1");
     return 255;
   }
+  if (sched != "flooding" && sched != "layered") {
+    error("--schedule / KML_SCHEDULE must be flooding or layered");
+    return 255;
+  }
+  if (sched == "layered" && alg != "nms") {
+    error("--schedule layered needs --algorithm nms: the schedule belongs to the min-sum mode");
+    return 255;
+  }
   if (prec == "f32") info("BP decode precision: f32 (single precision, not bit-exact with the reference)");
   if (alg == "nms")
     info(fmt("BP decode algorithm: nms (normalized min-sum, alpha = %g; not the reference's decoder)",
              alpha > 0.0 ? (double)(float)alpha : 0.75));
+  if (sched == "layered") info("BP decode schedule: layered");
   info("Start simulation");
   {
     FILE *f = fopen(cfg.c_str(), "rb");
@@ -158,6 +175,11 @@ int main(int argc, char **argv) {
     return 255;
   }
   if (alg == "nms" && kml_set_algorithm(ctx, KML_ALG_NMS, alpha) != KML_OK) {
+    error(kml_last_error(ctx));
+    kml_destroy(ctx);
+    return 255;
+  }
+  if (sched == "layered" && kml_set_schedule(ctx, KML_SCHED_LAYERED) != KML_OK) {
     error(kml_last_error(ctx));
     kml_destroy(ctx);
     return 255;
