@@ -233,6 +233,71 @@ int kml_set_schedule(kml_ctx *ctx, int sched);
 int kml_get_schedule(const kml_ctx *ctx);
 int kml_code_layers(const kml_ctx *ctx, int32_t *layer_ptr, int cap);
 
+/* The LLR front end of the min-sum mode: a max-log demapper that writes float
+ * LLRs, min-sum decodes that take float LLRs and can return posteriors, and a
+ * per-context switch, a fourth axis beside precision, algorithm and schedule,
+ * that puts both on the receive path.  Like the min-sum mode it is a different
+ * receiver from the reference's: it is held to tests/bp_llr_model.py, which the
+ * kernels equal bit for bit, not to the reference.
+ * Max-log demapper (kml_demap_llr, kmldpc_amd/csrc/demap_llr.hip).  Every value
+ * is IEEE binary32 with denormals kept (the code object's float_denorm_mode_32
+ * is 3), no fma, each operation rounded once.  Rounded once to float on the way
+ * in: y[s] and h (fp64 in the interface), the normalised constellation points
+ * x_k (kml_constellation) and inv = (float)(1.0 / var), the division in fp64.
+ * Per symbol s and point k:
+ *   gr = hr*xr_k - hi*xi_k, gi = hr*xi_k + hi*xr_k, er = yr - gr, ei = yi - gi,
+ *   d_k = er*er + ei*ei;
+ * for bit i of the symbol (the label's bits most significant first, kml_demap's
+ * order: bit i of point k is (k >> (bits - 1 - i)) & 1)
+ *   L = (min over k with bit_i(k) = 1 of d_k - min over k with bit_i(k) = 0 of d_k) * inv
+ * at entry s*bits + i of the codeword, where kml_demap writes that bit's P0.
+ * Positive means bit 0, as log(P0 / P1) does.  No clamp and no clip: the output
+ * is the raw LLR.  kml_demap_llr works in any algorithm and on any code;
+ * KML_E_UNSUP on a host-only context, KML_E_ARG for a NULL pointer, B < 0 or a
+ * var that is not > 0.
+ * LLR-in decode (kml_llr_decode): llr[B][cc_len] floats.  The two min-sum
+ * contracts above with one change, the prior: L[v] = min(max(x, -256.0f),
+ * 256.0f) of the caller's float (+-inf and +-1e30 are +-256; a punctured 5G
+ * column has L = +0 as before).  A NaN is the caller's error: that codeword's
+ * result is unspecified, no other codeword's is.  For any P0, decoding the
+ * priors of the P0 contract through this entry equals kml_bp_decode of that P0
+ * bit for bit (|L| <= 27.7 there: the clamp does nothing).  Schedule and alpha
+ * are the context's; uu_hat, ret, cc_hat as in kml_bp_decode (any may be NULL).
+ * llr_out[B][Ncol] (optional, punctured columns included) receives the
+ * posteriors the returned decisions were taken from, as bit patterns (-0 and +0
+ * differ): in the flooding schedule the T of the VN phase whose decisions are
+ * returned, in the layered schedule T as the loop left it; iter_count = 0
+ * leaves it as passed.  KML_E_UNSUP: a host-only context, a context not in
+ * KML_ALG_NMS (so every code the min-sum mode refuses), and, for llr_out in the
+ * flooding schedule only, a code whose N more floats of LDS do not fit.
+ * The switch (kml_set_demapper).  KML_DEMAP_EXACT (the default, always
+ * accepted): every path runs what it ran before.  KML_DEMAP_MAXLOG: in
+ * kml_decode_frames, kml_decode_candidates, kml_sim_decode(_ex) and
+ * kml_sim_point the final decode demaps with the max-log demapper and decodes
+ * from its LLRs, on the known-channel and the blind path; for a 5G code the
+ * candidate metric decodes run the context's min-sum decoder too (its alpha and
+ * schedule, budget metric_iter) on the max-log LLRs of the candidates, the
+ * metric being the unsatisfied checks of the decisions returned.  So under the
+ * switch chosen and metrics of a 5G code are a min-sum receiver's, not the
+ * reference's.  For a non-5G code the hard metric on the exact demapper's
+ * output stays: chosen and metrics are bit-identical to the exact mode's and
+ * only the final decode's priors change.  k-means (h_hat) is untouched on every
+ * path; kml_demap and kml_bp_decode do not read the switch.
+ * KML_DEMAP_MAXLOG returns KML_E_UNSUP, and the context keeps its value, on a
+ * host-only context, on a context whose algorithm is not KML_ALG_NMS, and with
+ * KML_BP_KERNEL=generic; an unknown value returns KML_E_ARG.
+ * kml_set_algorithm(KML_ALG_SPA) returns the demapper to exact;
+ * kml_set_algorithm(KML_ALG_NMS, alpha) and kml_set_schedule keep it.  The
+ * min-sum mode's refusals (syn, the soft-syndrome metric,
+ * kml_sim_decode_profile) hold as they are.  There is no fallback. */
+#define KML_DEMAP_EXACT 0
+#define KML_DEMAP_MAXLOG 1
+int kml_set_demapper(kml_ctx *ctx, int demapper);
+int kml_get_demapper(const kml_ctx *ctx);
+int kml_demap_llr(kml_ctx *ctx, const double *y, const double *h, double var, int B, float *llr, int flags);
+int kml_llr_decode(kml_ctx *ctx, const float *llr, int B, int iter_count, uint8_t *uu_hat, int32_t *ret,
+                   uint8_t *cc_hat, float *llr_out, int flags);
+
 int kml_dims(const kml_ctx *ctx, int32_t *dims /* [KML_DIM_COUNT] */);
 /* Host-side code plan, for inspection and parity tests. */
 int kml_code_perm(const kml_ctx *ctx, int32_t *perm /* [Ncol] */);

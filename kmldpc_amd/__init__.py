@@ -33,6 +33,7 @@ KML_HISTOGRAM = 2
 PRECISIONS = {"f64": 0, "f32": 1}  # KML_PREC_F64, KML_PREC_F32
 ALGORITHMS = {"spa": 0, "nms": 1}  # KML_ALG_SPA, KML_ALG_NMS
 SCHEDULES = {"flooding": 0, "layered": 1}  # KML_SCHED_FLOODING, KML_SCHED_LAYERED
+DEMAPPERS = {"exact": 0, "maxlog": 1}  # KML_DEMAP_EXACT, KML_DEMAP_MAXLOG
 DIM_NAMES = ["M", "Ncol", "K", "cc_len", "Z", "E", "chk", "max_iter", "bits", "Kc", "S", "bp_lds", "part_group"]
 
 
@@ -86,6 +87,10 @@ def lib():
         "kml_set_schedule": (I, [P, I]),
         "kml_get_schedule": (I, [P]),
         "kml_code_layers": (I, [P, P, I]),
+        "kml_set_demapper": (I, [P, I]),
+        "kml_get_demapper": (I, [P]),
+        "kml_demap_llr": (I, [P, P, P, D, I, P, I]),
+        "kml_llr_decode": (I, [P, P, I, I, P, P, P, P, I]),
         "kml_create": (I, [C.c_char_p, C.c_char_p, I, PP]),
         "kml_create_explicit": (I, [C.c_char_p, C.c_char_p, I, I, I, I, I, I, PP]),
         "kml_destroy": (None, [P]),
@@ -176,7 +181,7 @@ class Context:
 
     def __init__(self, config=None, data_dir=None, device=0, *, matrix_file=None, modem_file=None, is5g=False,
                  active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64", algorithm="spa",
-                 schedule="flooding"):
+                 schedule="flooding", demapper="exact"):
         L = lib()
         h = C.c_void_p()
         if config is not None:
@@ -216,6 +221,12 @@ class Context:
         if schedule != "flooding":
             try:
                 self.set_schedule(schedule)
+            except Exception:
+                self.close()
+                raise
+        if demapper != "exact":
+            try:
+                self.set_demapper(demapper)
             except Exception:
                 self.close()
                 raise
@@ -288,6 +299,20 @@ class Context:
         v = int(lib().kml_get_schedule(self._h))
         return {n: k for k, n in SCHEDULES.items()}[v]
 
+    # ---- front end of the min-sum receive path (kml_set_demapper)
+    def set_demapper(self, demapper):
+        """"exact" (default, always accepted) or "maxlog" (opt-in, the min-sum mode only: the receive path demaps
+        to float LLRs with the max-log demapper and decodes from them, a 5G code's candidate metric decodes
+        included; its arithmetic is tests/bp_llr_model.py's bit for bit).  Raises KmlError with code -4 where it
+        is not available."""
+        # an unknown name reaches the library as an unknown value, which answers KML_E_ARG
+        self._chk(lib().kml_set_demapper(self._h, DEMAPPERS.get(demapper, -1)), f"kml_set_demapper({demapper!r})")
+
+    @property
+    def demapper(self):
+        v = int(lib().kml_get_demapper(self._h))
+        return {n: k for k, n in DEMAPPERS.items()}[v]
+
     def layers(self):
         """layer_ptr[nl + 1] of the layered schedule (kml_code_layers): layer l = rows [layer_ptr[l], layer_ptr[l + 1])."""
         nl = self._chk_count(lib().kml_code_layers(self._h, None, 0), "kml_code_layers")
@@ -351,6 +376,34 @@ class Context:
         p0 = np.zeros((B, self.cc_len))
         self._chk(lib().kml_demap(self._h, _p(y), _p(h), float(var), B, _p(p0), 0), "kml_demap")
         return p0
+
+    def demap_llr(self, y, h, var):
+        """The max-log demapper (kml_demap_llr): float32 LLRs [B, cc_len], positive = bit 0."""
+        y = _f64(y).reshape(-1, self.S, 2)
+        B = y.shape[0]
+        h = _f64(h).reshape(B, 2)
+        llr = np.zeros((B, self.cc_len), np.float32)
+        self._chk(lib().kml_demap_llr(self._h, _p(y), _p(h), float(var), B, _p(llr), 0), "kml_demap_llr")
+        return llr
+
+    def llr_decode(self, llr, iter_count=None, cc_hat=False, llr_out=False):
+        """The context's min-sum decoder on float32 LLR priors (kml_llr_decode); returns
+        dict(uu_hat, ret[, cc_hat, llr_out]), llr_out [B, Ncol] = the posteriors the decisions came from."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, self.cc_len)
+        B = llr.shape[0]
+        it = self.max_iter if iter_count is None else int(iter_count)
+        uh = np.zeros((B, self.K), np.uint8)
+        ret = np.zeros(B, np.int32)
+        cch = np.zeros((B, self.Ncol), np.uint8) if cc_hat else None
+        post = np.zeros((B, self.Ncol), np.float32) if llr_out else None
+        self._chk(lib().kml_llr_decode(self._h, _p(llr), B, it, _p(uh), _p(ret), _p(cch), _p(post), 0),
+                  "kml_llr_decode")
+        out = dict(uu_hat=uh, ret=ret)
+        if cc_hat:
+            out["cc_hat"] = cch
+        if llr_out:
+            out["llr_out"] = post
+        return out
 
     def kmeans(self, y, iters=20):
         y = _f64(y).reshape(-1, self.S, 2)

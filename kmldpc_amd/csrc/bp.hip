@@ -327,8 +327,12 @@ long long bp_gslots_needed(const DevCode &c) {
 }
 
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family,
-                     const LnmsPlanDev *lnms) {
+                     const LnmsPlanDev *lnms, const LlrIoDev *llr) {
   if (a.B <= 0) return hipSuccess;
+  if (llr && a.prec != 2 && a.prec != 3) {  // no other family reads float priors
+    if (err) *err = "the LLR front end belongs to the min-sum kernels";
+    return hipErrorNotSupported;
+  }
   if (a.iter_count < 0) {
     if (err) *err = "iter_count must be >= 0";
     return hipErrorInvalidValue;
@@ -352,7 +356,15 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
       if (err) *err = "the layered min-sum schedule needs the code's layer plan";
       return hipErrorNotSupported;
     }
-    hipError_t e = layered ? launch_bp_irregular_lnms(c, a, *lnms, s) : launch_bp_irregular_nms(c, a, s);
+    if (llr && llr->post && !layered && bp_irregular_nms_supported(c) && !bp_irregular_nms_post_supported(c)) {
+      if (err) *err = "the posterior output of the flooding min-sum kernel does not fit this code's LDS";
+      return hipErrorNotSupported;
+    }
+    hipError_t e;
+    if (llr)
+      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, *llr, s) : launch_bp_irregular_nms(c, a, *llr, s);
+    else
+      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, s) : launch_bp_irregular_nms(c, a, s);
     if (e == hipErrorNotSupported) {
       if (err)
         *err = layered ? "the layered min-sum BP kernel does not take this code or launch"

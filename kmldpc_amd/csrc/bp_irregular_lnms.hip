@@ -162,9 +162,19 @@ __device__ __forceinline__ bool lnms_parity_fail(const LnmsLds &s, int M, int g,
 // tables pass by pass.  Both compute the same.
 // Six waves per SIMD = two workgroups of 12 waves per CU.
 constexpr int kCachePasses = 12;
-template <int T, bool CACHED>
+
+// The LLR instances' extra kernel argument (none: the P0 instances).
+__device__ __forceinline__ const LlrIoDev &llr_io(const LlrIoDev &io) { return io; }
+
+// The instances without Llr are the P0 front end (the contract above).  With
+// one LlrIoDev argument the priors are the caller's floats, clamped to +-256
+// (there is no log in those instances), and POST also writes T, as the loop
+// left it, out with the decisions taken from it.
+template <int T, bool CACHED, bool POST = false, class... Llr>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void bp_irregular_lnms_kernel(
-    DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp) {
+    DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, Llr... io) {
+  constexpr bool LLR = sizeof...(Llr) > 0;
+  static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int g = tid / kLanes, l = tid % kLanes;
@@ -195,16 +205,23 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
     const int entry = red[3];
     if (entry >= B) break;
     const int cw = a.cw_idx ? a.cw_idx[entry] : entry;
-    const double *p0 = a.p0 + (long long)cw * a.p0_stride;
-    if (a.p0_sel) p0 += (long long)a.p0_sel[cw] * a.p0_sel_stride;
+    if constexpr (LLR) {
+      const float *in = llr_io(io...).llr + (long long)cw * a.p0_stride;
+      if (a.p0_sel) in += (long long)a.p0_sel[cw] * a.p0_sel_stride;
+      for (int v = tid; v < c.N; v += T)  // (a punctured column: +0)
+        post[v] = v >= c.punct ? fminf(fmaxf(in[v - c.punct], -kNmsClamp), kNmsClamp) : 0.0f;
+    } else {
+      const double *p0 = a.p0 + (long long)cw * a.p0_stride;
+      if (a.p0_sel) p0 += (long long)a.p0_sel[cw] * a.p0_sel_stride;
 
-    for (int v = tid; v < c.N; v += T) {
-      float L = 0.0f;  // a punctured column
-      if (v >= c.punct) {
-        const double q = fmin(fmax(p0[v - c.punct], kSmallestProb), 1.0 - kSmallestProb);
-        L = (float)(kml_log(q) - kml_log(1.0 - q));
+      for (int v = tid; v < c.N; v += T) {
+        float L = 0.0f;  // a punctured column
+        if (v >= c.punct) {
+          const double q = fmin(fmax(p0[v - c.punct], kSmallestProb), 1.0 - kSmallestProb);
+          L = (float)(kml_log(q) - kml_log(1.0 - q));
+        }
+        post[v] = L;
       }
-      post[v] = L;
     }
     for (int e = tid; e < c.E; e += T) c2v[e] = 0;  // messages start at +0
     // (filled per codeword, after the priors: held across kml_log they would spill)
@@ -268,6 +285,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
         uint8_t *o = a.cc_hat + (long long)cw * c.N;
         for (int v = tid; v < c.N; v += T) o[v] = cch[v];
       }
+      if constexpr (POST) {  // the posteriors hard was taken from
+        float *o = llr_io(io...).post + (long long)cw * c.N;
+        for (int v = tid; v < c.N; v += T) o[v] = post[v];
+      }
       if (a.parity_cnt) {  // ParityCheck(cc_hat) (:281-300)
         int cnt = 0;
         for (int r = tid; r < c.M; r += T) {
@@ -313,23 +334,49 @@ size_t lnms_lds_bytes(const DevCode &c, int npass) {
 
 }  // namespace
 
+namespace {
+// What both front ends check, and the launch shape they share: the dynamic LDS
+// and the workgroups per CU (0: the code or the launch is not this kernel's).
+int lnms_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, size_t &lds) {
+  if (!bp_irregular_nms_supported(c)) return 0;
+  if (a.syn || a.cw_prof || a.prof) return 0;  // no syndrom_soft, no profile (launch_bp says why)
+  // row degrees <= 2 * kLanes by bp_irregular_nms_supported; the u16 tables hold E, N and M
+  if (!lp.pass || lp.npass < 1 || c.dc_max > 2 * kLanes || c.E > 65535 || c.N >= (int)kNoCol || c.M > 65535) return 0;
+  lds = lnms_lds_bytes(c, lp.npass);
+  if (lds + sizeof(WgVotes) > kLdsLimit) return 0;
+  // two workgroups per CU where the LDS holds both (no scratch: DESIGN.md)
+  return 2 * (lds + sizeof(WgVotes) + 1024) <= kLdsLimit ? 2 : 1;
+}
+}  // namespace
+
 hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, hipStream_t s) {
   constexpr int T = kIrrThreads;
   static_assert(T / kLanes == kLayRowsPerPass, "the plan's passes are this kernel's");
-  if (!bp_irregular_nms_supported(c)) return hipErrorNotSupported;
-  if (a.syn || a.cw_prof || a.prof) return hipErrorNotSupported;  // no syndrom_soft, no profile (launch_bp says why)
-  // row degrees <= 2 * kLanes by bp_irregular_nms_supported; the u16 tables hold E, N and M
-  if (!lp.pass || lp.npass < 1 || c.dc_max > 2 * kLanes || c.E > 65535 || c.N >= (int)kNoCol || c.M > 65535)
-    return hipErrorNotSupported;
-  const size_t lds = lnms_lds_bytes(c, lp.npass);
-  if (lds + sizeof(WgVotes) > kLdsLimit) return hipErrorNotSupported;
-  // two workgroups per CU where the LDS holds both (no scratch: DESIGN.md)
-  const int per_cu = 2 * (lds + sizeof(WgVotes) + 1024) <= kLdsLimit ? 2 : 1;
+  size_t lds = 0;
+  const int per_cu = lnms_launch_shape(c, a, lp, lds);
+  if (!per_cu) return hipErrorNotSupported;
   if (lp.npass <= kCachePasses)
     return launch_persistent(bp_irregular_lnms_kernel<T, true>, T, lds, per_cu, kNoGridCap, false, a, s, c, a,
                              a.queue, lp);
   return launch_persistent(bp_irregular_lnms_kernel<T, false>, T, lds, per_cu, kNoGridCap, false, a, s, c, a,
                            a.queue, lp);
+}
+
+// The LLR front end: float priors (io.llr), and the posterior instances when io.post is set.
+hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev &io,
+                                    hipStream_t s) {
+  constexpr int T = kIrrThreads;
+  size_t lds = 0;
+  const int per_cu = lnms_launch_shape(c, a, lp, lds);
+  if (!per_cu || !io.llr) return hipErrorNotSupported;
+  auto go = [&](auto kern) {
+    return launch_persistent(kern, T, lds, per_cu, kNoGridCap, false, a, s, c, a, a.queue, lp, io);
+  };
+  if (lp.npass <= kCachePasses)
+    return io.post ? go(bp_irregular_lnms_kernel<T, true, true, LlrIoDev>)
+                   : go(bp_irregular_lnms_kernel<T, true, false, LlrIoDev>);
+  return io.post ? go(bp_irregular_lnms_kernel<T, false, true, LlrIoDev>)
+                 : go(bp_irregular_lnms_kernel<T, false, false, LlrIoDev>);
 }
 
 }  // namespace kml

@@ -62,8 +62,10 @@ __device__ __forceinline__ unsigned umin(unsigned a, unsigned b) { return a < b 
 __device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
 
 // One column of degree D: cs = its D slot indices in column order, L its prior.
-template <int D>
-__device__ __forceinline__ void nms_vn_col(int2 *slots, const unsigned short *cs, float L, unsigned char *hard) {
+// POST: T also goes to *tp (the posterior instance's LDS array).
+template <int D, bool POST>
+__device__ __forceinline__ void nms_vn_col(int2 *slots, const unsigned short *cs, float L, unsigned char *hard,
+                                           float *tp) {
   int s[D];
   float c[D];
 #pragma unroll
@@ -75,6 +77,7 @@ __device__ __forceinline__ void nms_vn_col(int2 *slots, const unsigned short *cs
   for (int k = 0; k < D; ++k) t = t + c[k];
   const int hb = t > 0.0f ? 0 : 1;
   *hard = (unsigned char)hb;
+  if constexpr (POST) *tp = t;
 #pragma unroll
   for (int k = 0; k < D; ++k) {
     const float q = fminf(fmaxf(t - c[k], -kNmsClamp), kNmsClamp);
@@ -84,18 +87,19 @@ __device__ __forceinline__ void nms_vn_col(int2 *slots, const unsigned short *cs
 
 // Degree dispatch.  d is in 1..9 (columns) and 2..10 (rows): irr_ok and the
 // maxima checked by bp_irregular_nms_supported; the default cases are 9 and 10.
+template <bool POST>
 __device__ __forceinline__ void nms_vn_any(int d, int2 *slots, const unsigned short *cs, float L,
-                                           unsigned char *hard) {
+                                           unsigned char *hard, float *tp) {
   switch (d) {
-    case 1: nms_vn_col<1>(slots, cs, L, hard); break;
-    case 2: nms_vn_col<2>(slots, cs, L, hard); break;
-    case 3: nms_vn_col<3>(slots, cs, L, hard); break;
-    case 4: nms_vn_col<4>(slots, cs, L, hard); break;
-    case 5: nms_vn_col<5>(slots, cs, L, hard); break;
-    case 6: nms_vn_col<6>(slots, cs, L, hard); break;
-    case 7: nms_vn_col<7>(slots, cs, L, hard); break;
-    case 8: nms_vn_col<8>(slots, cs, L, hard); break;
-    default: nms_vn_col<9>(slots, cs, L, hard); break;
+    case 1: nms_vn_col<1, POST>(slots, cs, L, hard, tp); break;
+    case 2: nms_vn_col<2, POST>(slots, cs, L, hard, tp); break;
+    case 3: nms_vn_col<3, POST>(slots, cs, L, hard, tp); break;
+    case 4: nms_vn_col<4, POST>(slots, cs, L, hard, tp); break;
+    case 5: nms_vn_col<5, POST>(slots, cs, L, hard, tp); break;
+    case 6: nms_vn_col<6, POST>(slots, cs, L, hard, tp); break;
+    case 7: nms_vn_col<7, POST>(slots, cs, L, hard, tp); break;
+    case 8: nms_vn_col<8, POST>(slots, cs, L, hard, tp); break;
+    default: nms_vn_col<9, POST>(slots, cs, L, hard, tp); break;
   }
 }
 
@@ -156,14 +160,23 @@ __device__ __forceinline__ unsigned nms_cn_any(int d, int2 *slots, int base, int
   }
 }
 
+__host__ __device__ inline size_t nms_lds_bytes(const DevCode &c) {
+  return (size_t)c.irr_slots * 8 + (size_t)c.cc_len * 4 + (size_t)c.E * 2 + kRedBytes + (size_t)c.N;
+}
+// ... and with the posterior instance's N floats behind it
+size_t nms_post_lds_bytes(const DevCode &c) { return ((nms_lds_bytes(c) + 3) & ~(size_t)3) + (size_t)c.N * 4; }
+
+// The LLR instances' extra kernel argument (none: the P0 instances).
+__device__ __forceinline__ const LlrIoDev &llr_io(const LlrIoDev &io) { return io; }
+
 // The iterations of one codeword (bp_irregular.hip decode_irr without its
 // FAST / SYN / PROF parts).  Each lane's plan is packed into one word per
 // round (slot base | degree << 14 | column or row << 18; ~0 = no item).
-template <int T>
+template <int T, bool POST>
 __device__ __forceinline__ void decode_nms(const DevCode &c, const BpLaunch &a, int2 *slots,
-                                           const unsigned short *cslot, const float *pri, unsigned char *cch, int odd,
-                                           const int (&vcol)[3], const int (&crow)[3], int &iter_out,
-                                           bool &conv_out) {
+                                           const unsigned short *cslot, const float *pri, unsigned char *cch,
+                                           float *tpost, int odd, const int (&vcol)[3], const int (&crow)[3],
+                                           int &iter_out, bool &conv_out) {
   unsigned vpk[3], cpk[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
@@ -192,7 +205,7 @@ __device__ __forceinline__ void decode_nms(const DevCode &c, const BpLaunch &a, 
       if (vpk[r] != ~0u) {
         const int v = pitem(vpk[r]);
         const float L = v >= c.punct ? pri[v - c.punct] : 0.0f;
-        nms_vn_any(pdeg(vpk[r]), slots, cslot + pbase(vpk[r]), L, &cch[v]);
+        nms_vn_any<POST>(pdeg(vpk[r]), slots, cslot + pbase(vpk[r]), L, &cch[v], POST ? &tpost[v] : nullptr);
       }
     __syncthreads();
     // The early-stop parity of each row comes out of the CN pass (the decisions
@@ -212,8 +225,14 @@ __device__ __forceinline__ void decode_nms(const DevCode &c, const BpLaunch &a, 
   conv_out = conv;
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch a, unsigned int *queue) {
+// The instance without Llr is the P0 front end (the contract above).  With one
+// LlrIoDev argument the priors are the caller's floats, clamped to +-256 (there
+// is no log in that instance), and POST also keeps the T of every VN phase in N
+// more floats of LDS and writes the last one out with the decisions.
+template <int T, bool POST = false, class... Llr>
+__global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch a, unsigned int *queue, Llr... io) {
+  constexpr bool LLR = sizeof...(Llr) > 0;
+  static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int odd = tid & 1;
@@ -223,6 +242,8 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
   int *red = reinterpret_cast<int *>(smem + sb + (size_t)c.cc_len * 4);
   unsigned short *cslot = reinterpret_cast<unsigned short *>(smem + sb + (size_t)c.cc_len * 4 + kRedBytes);
   unsigned char *cch = smem + sb + (size_t)c.cc_len * 4 + kRedBytes + (size_t)c.E * 2;
+  float *tpost = nullptr;  // POST: [N], behind the decision bytes
+  if constexpr (POST) tpost = reinterpret_cast<float *>(smem + ((nms_lds_bytes(c) + 3) & ~(size_t)3));
 
   for (int e = tid; e < c.E; e += T) cslot[e] = (unsigned short)c.irr_col_slot[e];
   int vcol[3], crow[3];
@@ -244,19 +265,25 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
     const int entry = red[3];
     if (entry >= B) break;
     const int cw = a.cw_idx ? a.cw_idx[entry] : entry;
-    const double *p0 = a.p0 + (long long)cw * a.p0_stride;
-    if (a.p0_sel) p0 += (long long)a.p0_sel[cw] * a.p0_sel_stride;
+    if constexpr (LLR) {
+      const float *l = llr_io(io...).llr + (long long)cw * a.p0_stride;
+      if (a.p0_sel) l += (long long)a.p0_sel[cw] * a.p0_sel_stride;
+      for (int i = tid; i < c.cc_len; i += T) pri[i] = fminf(fmaxf(l[i], -kNmsClamp), kNmsClamp);
+    } else {
+      const double *p0 = a.p0 + (long long)cw * a.p0_stride;
+      if (a.p0_sel) p0 += (long long)a.p0_sel[cw] * a.p0_sel_stride;
 
-    for (int i = tid; i < c.cc_len; i += T) {
-      const double q = fmin(fmax(p0[i], kSmallestProb), 1.0 - kSmallestProb);
-      pri[i] = (float)(kml_log(q) - kml_log(1.0 - q));
+      for (int i = tid; i < c.cc_len; i += T) {
+        const double q = fmin(fmax(p0[i], kSmallestProb), 1.0 - kSmallestProb);
+        pri[i] = (float)(kml_log(q) - kml_log(1.0 - q));
+      }
     }
     for (int e = tid; e < c.irr_slots; e += T) slots[e] = make_int2(0, 0);  // messages start at +0
     __syncthreads();  // the first VN phase reads priors and slots other threads wrote
 
     int iter = 0;
     bool conv = false;
-    decode_nms<T>(c, a, slots, cslot, pri, cch, odd, vcol, crow, iter, conv);
+    decode_nms<T, POST>(c, a, slots, cslot, pri, cch, tpost, odd, vcol, crow, iter, conv);
 
     if (a.iter_count > 0) {
       if (a.uu_hat) {
@@ -266,6 +293,10 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
       if (a.cc_hat) {
         uint8_t *o = a.cc_hat + (long long)cw * c.N;
         for (int v = tid; v < c.N; v += T) o[v] = cch[v];
+      }
+      if constexpr (POST) {  // the T of the VN phase these decisions came from
+        float *o = llr_io(io...).post + (long long)cw * c.N;
+        for (int v = tid; v < c.N; v += T) o[v] = tpost[v];
       }
       if (a.parity_cnt) {  // ParityCheck(cc_hat) (:281-300)
         int cnt = 0;
@@ -305,10 +336,6 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
   }
 }
 
-size_t nms_lds_bytes(const DevCode &c) {
-  return (size_t)c.irr_slots * 8 + (size_t)c.cc_len * 4 + (size_t)c.E * 2 + kRedBytes + (size_t)c.N;
-}
-
 }  // namespace
 
 // The codes of launch_bp_irregular (bp_irregular.hip): irr_ok, a round plan,
@@ -331,6 +358,24 @@ hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, hipStrea
   if (a.syn || a.cw_prof || a.prof) return hipErrorNotSupported;  // no syndrom_soft, no profile (launch_bp says why)
   auto kern = bp_irregular_nms_kernel<T>;
   return launch_persistent(kern, T, nms_lds_bytes(c), 1, kNoGridCap, false, a, s, c, a, a.queue);
+}
+
+bool bp_irregular_nms_post_supported(const DevCode &c) {
+  return bp_irregular_nms_supported(c) && nms_post_lds_bytes(c) <= kLdsLimit;
+}
+
+// The LLR front end: float priors (io.llr), and the posterior instance when io.post is set.
+hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const LlrIoDev &io, hipStream_t s) {
+  constexpr int T = kIrrThreads;
+  if (!bp_irregular_nms_supported(c) || !io.llr) return hipErrorNotSupported;
+  if (a.syn || a.cw_prof || a.prof) return hipErrorNotSupported;
+  if (io.post) {
+    if (!bp_irregular_nms_post_supported(c)) return hipErrorNotSupported;
+    return launch_persistent(bp_irregular_nms_kernel<T, true, LlrIoDev>, T, nms_post_lds_bytes(c), 1, kNoGridCap, false,
+                             a, s, c, a, a.queue, io);
+  }
+  return launch_persistent(bp_irregular_nms_kernel<T, false, LlrIoDev>, T, nms_lds_bytes(c), 1, kNoGridCap, false, a, s,
+                           c, a, a.queue, io);
 }
 
 }  // namespace kml

@@ -183,6 +183,7 @@ int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
   if (alg == KML_ALG_SPA) {  // always accepted, alpha ignored; the schedule belongs to the min-sum mode
     c->algorithm = alg;
     c->schedule = KML_SCHED_FLOODING;
+    c->demapper = KML_DEMAP_EXACT;  // ... and so does the max-log front end
     return KML_OK;
   }
   if (alpha == 0.0) alpha = 0.75;
@@ -245,6 +246,29 @@ int kml_code_layers(const kml_ctx *c, int32_t *layer_ptr, int cap) {
   for (int i = 0; i < n; i++) layer_ptr[i] = lp[i];
   return (int)lp.size() - 1;
 }
+
+int kml_set_demapper(kml_ctx *c, int demapper) {
+  if (!c) return KML_E_ARG;
+  call_begin(c);
+  if (demapper != KML_DEMAP_EXACT && demapper != KML_DEMAP_MAXLOG)
+    return fail(c, KML_E_ARG, "kml_set_demapper: unknown demapper " + std::to_string(demapper));
+  if (demapper == KML_DEMAP_EXACT) {  // always accepted
+    c->demapper = demapper;
+    return KML_OK;
+  }
+  if (c->device < 0 || !c->stream)
+    return fail(c, KML_E_UNSUP, "kml_set_demapper: a host-only context (device < 0) has no min-sum decoder");
+  if (kml::bp_generic_forced())
+    return fail(c, KML_E_UNSUP, "kml_set_demapper: the max-log front end is not available with KML_BP_KERNEL=generic");
+  if (c->algorithm != KML_ALG_NMS)
+    return fail(c, KML_E_UNSUP,
+                "kml_set_demapper: the max-log front end belongs to the min-sum mode (kml_set_algorithm(KML_ALG_NMS) "
+                "first); the context keeps its demapper");
+  c->demapper = demapper;
+  return KML_OK;
+}
+
+int kml_get_demapper(const kml_ctx *c) { return c ? c->demapper : KML_E_ARG; }
 
 int kml_dims(const kml_ctx *c, int32_t *d) {
   if (!c || !d) return KML_E_ARG;
@@ -350,6 +374,74 @@ int kml_demap(kml_ctx *c, const double *y, const double *h, double var, int B, d
   TRY(stage_out(c, c->w_p0, p0, (size_t)B * c->code.cc_len, flags, o));
   TRY(run_demap(c, as_c(d_y), 1, as_c(d_h), 1, nullptr, var, B, o.dev));
   TRY(copy_out(c, o));
+  return sync(c);
+}
+
+int kml_demap_llr(kml_ctx *c, const double *y, const double *h, double var, int B, float *llr, int flags) {
+  const bool ok = c && y && h && llr && B >= 0 && var > 0.0;
+  if (ok && (c->device < 0 || !c->stream)) {
+    call_begin(c);
+    return fail(c, KML_E_UNSUP, "kml_demap_llr: host-only context (device < 0): no GPU operations");
+  }
+  if (ok && B == 0) return KML_OK;
+  TRY(gpu_begin(c, ok, "kml_demap_llr: bad argument"));
+  const int S = c->code.cc_len / c->modem.bits;
+  const double *d_y, *d_h;
+  TRY(stage_in(c, c->w_y, y, (size_t)B * S * 2, flags, d_y));
+  TRY(stage_in(c, c->w_h, h, (size_t)B * 2, flags, d_h));
+  Out<float> o;
+  TRY(stage_out(c, c->w_llr, llr, (size_t)B * c->code.cc_len, flags, o));
+  TRY(run_demap_llr(c, as_c(d_y), 1, as_c(d_h), 1, nullptr, var, B, o.dev));
+  TRY(copy_out(c, o));
+  return sync(c);
+}
+
+int kml_llr_decode(kml_ctx *c, const float *llr, int B, int iter_count, uint8_t *uu_hat, int32_t *ret, uint8_t *cc_hat,
+                   float *llr_out, int flags) {
+  const bool ok = c && llr && B >= 0 && iter_count >= 0;
+  if (ok) {  // the refusals, before anything is staged or launched
+    call_begin(c);
+    if (c->device < 0 || !c->stream)
+      return fail(c, KML_E_UNSUP, "kml_llr_decode: a host-only context (device < 0) has no min-sum decoder");
+    if (c->algorithm != KML_ALG_NMS)
+      return fail(c, KML_E_UNSUP,
+                  "kml_llr_decode: float LLRs are decoded by the min-sum mode only (kml_set_algorithm(KML_ALG_NMS) "
+                  "first)");
+    if (llr_out && c->schedule == KML_SCHED_FLOODING && !kml::bp_irregular_nms_post_supported(c->dc))
+      return fail(c, KML_E_UNSUP,
+                  "kml_llr_decode: the flooding kernel's posterior output (N more floats of LDS) does not fit this code; "
+                  "llr_out must be NULL");
+  }
+  if (ok && B == 0) return KML_OK;
+  TRY(gpu_begin(c, ok, "kml_llr_decode: bad argument"));
+  const kml::LdpcCode &L = c->code;
+  const float *d_llr;
+  TRY(stage_in(c, c->w_llr, llr, (size_t)B * L.cc_len, flags, d_llr));
+  Out<uint8_t> uh, cch;
+  Out<int32_t> rt;
+  Out<float> po;
+  TRY(stage_out(c, c->w_uh, uu_hat, (size_t)B * L.K, flags, uh));
+  TRY(stage_out(c, c->w_ret, ret, (size_t)B, flags, rt));
+  TRY(stage_out(c, c->w_cch, cc_hat, (size_t)B * L.N, flags, cch));
+  TRY(stage_out(c, c->w_post, llr_out, (size_t)B * L.N, flags, po));
+  kml::BpLaunch a;
+  a.B = B;
+  a.iter_count = iter_count;
+  a.max_iter = c->rc.max_iter;
+  a.p0_stride = L.cc_len;
+  a.uu_hat = uh.dev;
+  a.ret = rt.dev;
+  a.cc_hat = cch.dev;
+  kml::LlrIoDev lio;
+  lio.llr = d_llr;
+  lio.post = po.dev;
+  TRY(run_bp(c, a, nullptr, -1, false, &lio));
+  if (iter_count > 0) {  // with iter_count = 0 the kernels write none of these: the caller's arrays stay
+    TRY(copy_out(c, uh));
+    TRY(copy_out(c, cch));
+    TRY(copy_out(c, po));
+  }
+  TRY(copy_out(c, rt));
   return sync(c);
 }
 

@@ -74,6 +74,7 @@ struct kml_ctx {
   int algorithm = KML_ALG_SPA;      // kml_set_algorithm: decoder of the final BP decodes
   float nms_alpha = 0.75f;          // ... and the min-sum normalisation factor
   int schedule = KML_SCHED_FLOODING;  // kml_set_schedule: row schedule of the min-sum decodes
+  int demapper = KML_DEMAP_EXACT;   // kml_set_demapper: front end of the min-sum receive path
   kml::LayeredPlan layered;         // its layers (empty: the code has none, kml_code_layers says KML_E_UNSUP)
   kml::LnmsPlanDev lnms_dev;        // ... and the device copy of the passes (d_lnms)
   hipStream_t stream = nullptr;
@@ -105,6 +106,7 @@ struct kml_ctx {
   // workspaces
   DBuf w_y, w_h, w_h4, w_hhat, w_p0, w_uu, w_uh, w_uh4, w_ret, w_cch, w_syn, w_sel, w_met, w_pc, w_km, w_cwerr;
   DBuf w_prof, w_cwprof;  // kml_sim_decode_profile: prof[P][3], cw_prof[B][P]
+  DBuf w_llr, w_post;     // the LLR front end: float priors (demap_llr's output), posteriors
   // soft syndrome metric: candidate / final syndromes, iteration counts, sums, decode lists
   DBuf s_synm, s_synf, s_itm, s_itf, s_Lm, s_Lf, s_list;
   // Sum of log(syndrom_soft) of the most recent decode that ran a CN phase on
@@ -204,13 +206,21 @@ int read_back(kml_ctx *c, const unsigned long long *cnt, uint64_t *counters, int
 // metric = true: a candidate-metric decode of the blind front end, which stays
 // fp64 sum-product in every mode (kml_set_precision and kml_set_algorithm
 // change the final decodes only).
-int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out = nullptr, int reuse = -1, bool metric = false);
+// llr: decode from float priors (kernels.hpp LlrIoDev) with the context's
+// min-sum decoder, whose mode the context must be in; a.p0 is not read and
+// a.p0_stride / a.p0_sel_stride count floats.  The max-log front end's
+// candidate-metric decodes come this way too (metric stays false).
+int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out = nullptr, int reuse = -1, bool metric = false,
+           const kml::LlrIoDev *llr = nullptr);
 // The FAST demappers' defer list (kernels.hpp DemapDefer): at least `need`
 // entries (the candidate metric defers whole codewords: need = B).
 int demap_defer(kml_ctx *c, int need, kml::DemapDefer &d);
 // launch_demap as one profiled "demap" stage (arguments as launch_demap's).
 int run_demap(kml_ctx *c, const double2 *y, int reps, const double2 *h, int h_stride, const int32_t *h_sel, double var,
               int n, double *p0);
+// launch_demap_llr as one profiled "demap" stage (arguments as run_demap's, float LLRs out).
+int run_demap_llr(kml_ctx *c, const double2 *y, int reps, const double2 *h, int h_stride, const int32_t *h_sel,
+                  double var, int n, float *llr);
 // launch_kmeans as one profiled "kmeans" stage; its workspace is the context's.
 int run_kmeans(kml_ctx *c, const double2 *y, int iters, int B, double2 *h_hat, double2 *h4, double2 *hat_out = nullptr);
 

@@ -326,7 +326,9 @@ int read_back(kml_ctx *c, const unsigned long long *cnt, uint64_t *counters, int
   return KML_OK;
 }
 
-int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric) {
+int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric, const kml::LlrIoDev *llr) {
+  if (llr && (metric || c->algorithm != KML_ALG_NMS))  // (callers check first: no fp64 kernel reads float priors)
+    return fail(c, KML_E_UNSUP, "float LLR priors are decoded by the min-sum mode (KML_ALG_NMS) only");
   a.prec = metric ? KML_PREC_F64 : c->precision;
   if (!metric && c->algorithm == KML_ALG_NMS) {  // (never with the f32 precision: kml_set_algorithm)
     if (a.syn) return fail(c, KML_E_UNSUP, "the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
@@ -354,7 +356,7 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric) {
   }
   Timer t(c, "bp", slot, (double)a.B * 8.0 * c->code.cc_len);
   const char *msg = nullptr;
-  hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family, &c->lnms_dev);
+  hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family, &c->lnms_dev, llr);
   t.stop();
   if (e != hipSuccess) return msg ? fail(c, KML_E_UNSUP, msg) : hip_fail(c, e, "bp launch");
   if (c->inject_abort >= 0 && c->coop_groups > 0 && c->inject_abort-- == 0)  // as if a group barrier timed out
@@ -387,6 +389,17 @@ int run_demap(kml_ctx *c, const double2 *y, int reps, const double2 *h, int h_st
   HIPCHK(c, kml::launch_demap(c->modem.bits, c->d_cons.as<double>(), y, S, reps, h, h_stride, h_sel, var, n, p0, dd,
                               c->stream),
          "demap");
+  t.stop();
+  return KML_OK;
+}
+
+int run_demap_llr(kml_ctx *c, const double2 *y, int reps, const double2 *h, int h_stride, const int32_t *h_sel,
+                  double var, int n, float *llr) {
+  const int S = c->code.cc_len / c->modem.bits;
+  Timer t(c, "demap", -1, (double)n * S * (16.0 + 4.0 * c->modem.bits));
+  HIPCHK(c, kml::launch_demap_llr(c->modem.bits, c->d_cons.as<double>(), y, S, reps, h, h_stride, h_sel,
+                                  (float)(1.0 / var), n, llr, c->stream),
+         "demap_llr");
   t.stop();
   return KML_OK;
 }

@@ -157,7 +157,22 @@ struct LnmsPlanDev {
   const int32_t *pass = nullptr;  // LayeredPlan::pass, device copy
   int npass = 0;
 };
+// The LLR front end of the two min-sum kernels (prec = 2 and 3 only): float
+// priors in place of BpLaunch::p0, with p0's addressing (p0_stride and
+// p0_sel_stride then count floats; p0_sel and cw_idx as they are), and an
+// optional posterior output.  Like LnmsPlanDev it travels as a kernel argument
+// of its own, and only the instances that read it take it: BpLaunch, DevCode
+// and the existing instances' kernarg segments stay as they are.
+struct LlrIoDev {
+  const float *llr = nullptr;  // priors: L[v] = min(max(llr[v - punct], -256), 256), +0 for a punctured column
+  float *post = nullptr;       // [B][N] posteriors the decisions were taken from (optional; iter_count = 0 writes none)
+};
+hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const LlrIoDev &io, hipStream_t s);
+// Does the flooding kernel's posterior instance (N more floats of LDS) fit this code?
+bool bp_irregular_nms_post_supported(const DevCode &c);
 hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, hipStream_t s);
+hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev &io,
+                                    hipStream_t s);
 // KML_BP_KERNEL=generic (read now, and as the dispatch first read it).
 bool bp_generic_forced();
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of
@@ -181,8 +196,9 @@ hipError_t bp_coop_raise_abort(const BpLaunch &a, int groups, hipStream_t s);
 int bp_regular_threads(int N, int M, int E, int dv_max, int dc_max, int regular);
 // family (optional) receives the name of the kernel that was launched.
 // lnms: the layer plan, read by prec = 3 only (which fails without one).
+// llr: the LLR front end (prec = 2 and 3 only; any other prec fails with it).
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err,
-                     const char **family = nullptr, const LnmsPlanDev *lnms = nullptr);
+                     const char **family = nullptr, const LnmsPlanDev *lnms = nullptr, const LlrIoDev *llr = nullptr);
 // Workspace the BP launcher needs in global-slot mode (double2 elements).
 long long bp_gslots_needed(const DevCode &c);
 bool bp_uses_lds(const DevCode &c);
@@ -201,6 +217,12 @@ struct DemapDefer {
 hipError_t launch_demap(int bits, const double *cons, const double2 *y, int S, int reps, const double2 *h,
                         int h_stride, const int32_t *h_sel, double var, int n, double *p0, const DemapDefer &d,
                         hipStream_t s);
+
+// The max-log demapper (demap_llr.hip): launch_demap's addressing (entry e
+// reads y row e / reps and channel h[e * h_stride + (h_sel ? h_sel[e] : 0)]),
+// float LLRs out, llr row e of S * bits floats.  inv = (float)(1.0 / var).
+hipError_t launch_demap_llr(int bits, const double *cons, const double2 *y, int S, int reps, const double2 *h,
+                            int h_stride, const int32_t *h_sel, float inv, int n, float *llr, hipStream_t s);
 
 // Hard-metric candidates for the PEG blind path (kmcodec.cc:105-119):
 // for each codeword and each of its nc (1 or 4) channel estimates h4[b][j], the

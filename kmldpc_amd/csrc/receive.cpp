@@ -54,23 +54,49 @@ int demap_then_bp(kml_ctx *c, kml::BpLaunch a, const double2 *y, const double2 *
   return run_bp(c, a, &bp_slot);
 }
 
+// The max-log front end (KML_DEMAP_MAXLOG, the min-sum mode only).
+bool maxlog(const kml_ctx *c) { return c->demapper == KML_DEMAP_MAXLOG && c->algorithm == KML_ALG_NMS; }
+
+// demap_then_bp under it: float LLRs from demap_llr into w_llr, decoded by the
+// context's min-sum kernel (there is no fused form).
+int demap_llr_then_bp(kml_ctx *c, kml::BpLaunch a, const double2 *y, const double2 *h, int h_stride,
+                      const int32_t *h_sel, double var, int &bp_slot) {
+  const size_t cc = (size_t)c->code.cc_len;
+  HIPCHK(c, c->w_llr.ensure(sizeof(float) * cc * a.B), "hipMalloc(llr)");
+  TRY(run_demap_llr(c, y, 1, h, h_stride, h_sel, var, a.B, c->w_llr.as<float>()));
+  kml::LlrIoDev lio;
+  lio.llr = c->w_llr.as<float>();
+  a.p0_stride = (long long)cc;
+  return run_bp(c, a, &bp_slot, -1, false, &lio);
+}
+
 // The candidates' metric decodes (5G hard metric and soft metric): P0 of all
 // nc * B candidates into w_p0, then BP for metric_iter iterations with the
 // outputs `m` asks for.  Histogram mode keeps their uu_hat (w_uh4): CntErr
-// reads the last candidate's.
+// reads the last candidate's.  Under KML_DEMAP_MAXLOG (5G hard metric only: the
+// soft metric is refused in the min-sum mode) the candidates' max-log LLRs go
+// into w_llr instead and the context's min-sum decoder runs the metric_iter
+// iterations.
 int metric_decodes(kml_ctx *c, const RecvIO &io, double var, int B, const double2 *hc, int nc, kml::BpLaunch &m) {
   const size_t cc = (size_t)c->code.cc_len, nB = (size_t)nc * B;
-  HIPCHK(c, c->w_p0.ensure(sizeof(double) * cc * nB), "hipMalloc(p0)");
-  TRY(run_demap(c, io.y, nc, hc, 1, nullptr, var, (int)nB, c->w_p0.as<double>()));
   m.B = (int)nB;
   m.iter_count = c->rc.metric_iter;
   m.max_iter = c->rc.max_iter;
-  m.p0 = c->w_p0.as<double>();
   m.p0_stride = (long long)cc;
   if (io.histogram) {
     HIPCHK(c, c->w_uh4.ensure(nB * c->code.K), "hipMalloc(uh4)");
     m.uu_hat = c->w_uh4.as<uint8_t>();
   }
+  if (maxlog(c)) {  // max-log LLRs of the candidates into w_llr, the context's min-sum decoder
+    HIPCHK(c, c->w_llr.ensure(sizeof(float) * cc * nB), "hipMalloc(llr)");
+    TRY(run_demap_llr(c, io.y, nc, hc, 1, nullptr, var, (int)nB, c->w_llr.as<float>()));
+    kml::LlrIoDev lio;
+    lio.llr = c->w_llr.as<float>();
+    return run_bp(c, m, nullptr, -1, false, &lio);
+  }
+  HIPCHK(c, c->w_p0.ensure(sizeof(double) * cc * nB), "hipMalloc(p0)");
+  TRY(run_demap(c, io.y, nc, hc, 1, nullptr, var, (int)nB, c->w_p0.as<double>()));
+  m.p0 = c->w_p0.as<double>();
   return run_bp(c, m, nullptr, -1, true);
 }
 
@@ -182,8 +208,17 @@ int receive(kml_ctx *c, const RecvIO &io, double snr, int B, int &bp_slot) {
   if (c->algorithm == KML_ALG_NMS && c->rc.metric_soft && !(io.true_h && !io.histogram))
     return fail(c, KML_E_UNSUP,
                 "the soft-syndrome metric (metric_type = 1) is not available in the min-sum mode (KML_ALG_NMS)");
+  // KML_DEMAP_MAXLOG: the final decode's priors, and a 5G code's candidate
+  // metric decodes, come from demap_llr and run the context's min-sum decoder;
+  // k-means, the hard metric of a non-5G code, launch_select and the histogram
+  // tail are the exact mode's
+  const bool llr = maxlog(c);
+  auto demap_bp = [&](const double2 *h, int h_stride, const int32_t *h_sel) {
+    return llr ? demap_llr_then_bp(c, final_launch(c, io, B), io.y, h, h_stride, h_sel, var, bp_slot)
+               : demap_then_bp(c, final_launch(c, io, B), io.y, h, h_stride, h_sel, var, bp_slot);
+  };
   if (io.true_h && !io.histogram)  // known channel: no candidates, no metric
-    return demap_then_bp(c, final_launch(c, io, B), io.y, io.true_h, 1, nullptr, var, bp_slot);
+    return demap_bp(io.true_h, 1, nullptr);
   // candidate channel estimates: the caller's, the true h (histogram on the
   // known-H path), or k-means + 4 rotations (simulator.cc:136-148)
   const double2 *hc = io.cand ? io.cand : io.true_h;
@@ -217,7 +252,7 @@ int receive(kml_ctx *c, const RecvIO &io, double snr, int B, int &bp_slot) {
            "cand_metric");
     t.stop();
     if (io.histogram) return histogram_tail(c, io, B, 0, hist_cnt);
-    return demap_then_bp(c, final_launch(c, io, B), io.y, hc, nc, chosen, var, bp_slot);
+    return demap_bp(hc, nc, chosen);
   }
   // 5G: metric = parity count after metric_iter BP iterations (kmcodec.cc:157-160)
   HIPCHK(c, c->w_pc.ensure(sizeof(int32_t) * nc * B), "hipMalloc(pc)");
@@ -226,6 +261,11 @@ int receive(kml_ctx *c, const RecvIO &io, double snr, int B, int &bp_slot) {
   TRY(metric_decodes(c, io, var, B, hc, nc, m));
   HIPCHK(c, kml::launch_select(m.parity_cnt, nc, B, met, chosen, c->stream), "select");
   if (io.histogram) return histogram_tail(c, io, B, nc, hist_cnt);
+  if (llr) {  // the chosen candidate's LLRs are in w_llr, addressed as its P0 would be in w_p0
+    kml::LlrIoDev lio;
+    lio.llr = c->w_llr.as<float>();
+    return run_bp(c, final_launch(c, io, B, nc, chosen), &bp_slot, -1, false, &lio);
+  }
   return run_bp(c, final_launch(c, io, B, nc, chosen), &bp_slot);
 }
 

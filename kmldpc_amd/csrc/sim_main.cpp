@@ -23,7 +23,9 @@
 // mode in its first line), KML_SCHEDULE (flooding or layered, also
 // `--schedule flooding|layered`: the row schedule of the min-sum decodes,
 // kml_set_schedule; layered needs nms and states itself in the line after the
-// algorithm's).
+// algorithm's), KML_DEMAPPER (exact or maxlog, also `--demapper exact|maxlog`:
+// the front end of the min-sum receive path, kml_set_demapper; maxlog needs nms
+// and states itself in the line after the schedule's).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -103,6 +105,7 @@ int main(int argc, char **argv) {
   std::string cfg = "config.toml", prec = getenv("KML_PRECISION") ? getenv("KML_PRECISION") : "f64";
   std::string alg = getenv("KML_ALGORITHM") ? getenv("KML_ALGORITHM") : "spa";
   std::string sched = getenv("KML_SCHEDULE") ? getenv("KML_SCHEDULE") : "flooding";
+  std::string demapper = getenv("KML_DEMAPPER") ? getenv("KML_DEMAPPER") : "exact";
   for (int i = 1; i < argc; i++) {
     const std::string arg = argv[i];
     if (arg == "--precision" && i + 1 < argc)
@@ -117,6 +120,10 @@ int main(int argc, char **argv) {
       sched = argv[++i];
     else if (arg.rfind("--schedule=", 0) == 0)
       sched = arg.substr(11);
+    else if (arg == "--demapper" && i + 1 < argc)
+      demapper = argv[++i];
+    else if (arg.rfind("--demapper=", 0) == 0)
+      demapper = arg.substr(11);
     else
       cfg = arg;
   }
@@ -145,11 +152,20 @@ int main(int argc, char **argv) {
     error("--schedule layered needs --algorithm nms: the schedule belongs to the min-sum mode");
     return 255;
   }
+  if (demapper != "exact" && demapper != "maxlog") {
+    error("--demapper / KML_DEMAPPER must be exact or maxlog");
+    return 255;
+  }
+  if (demapper == "maxlog" && alg != "nms") {
+    error("--demapper maxlog needs --algorithm nms: the max-log front end belongs to the min-sum mode");
+    return 255;
+  }
   if (prec == "f32") info("BP decode precision: f32 (single precision, not bit-exact with the reference)");
   if (alg == "nms")
     info(fmt("BP decode algorithm: nms (normalized min-sum, alpha = %g; not the reference's decoder)",
              alpha > 0.0 ? (double)(float)alpha : 0.75));
   if (sched == "layered") info("BP decode schedule: layered");
+  if (demapper == "maxlog") info("Demapper: maxlog (max-log LLR front end; not the reference's demapper)");
   info("Start simulation");
   {
     FILE *f = fopen(cfg.c_str(), "rb");
@@ -180,6 +196,11 @@ int main(int argc, char **argv) {
     return 255;
   }
   if (sched == "layered" && kml_set_schedule(ctx, KML_SCHED_LAYERED) != KML_OK) {
+    error(kml_last_error(ctx));
+    kml_destroy(ctx);
+    return 255;
+  }
+  if (demapper == "maxlog" && kml_set_demapper(ctx, KML_DEMAP_MAXLOG) != KML_OK) {
     error(kml_last_error(ctx));
     kml_destroy(ctx);
     return 255;

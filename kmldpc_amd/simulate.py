@@ -76,10 +76,10 @@ class Simulator:
     """Simulator (include/simulator.h): constructed from config.toml, Simulate() runs the sweep."""
 
     def __init__(self, config, data_dir=None, device=0, batch=32768, seed=0, dist=None, log=None, comm_backend="nccl",
-                 precision="f64", algorithm="spa", schedule="flooding"):
+                 precision="f64", algorithm="spa", schedule="flooding", demapper="exact"):
         self.log = log or Logger(enabled=(dist.get_rank() if dist else 0) == 0)
         self.ctx = Context(config, data_dir=data_dir or os.path.dirname(os.path.abspath(config)), device=device,
-                           precision=precision, algorithm=algorithm, schedule=schedule)
+                           precision=precision, algorithm=algorithm, schedule=schedule, demapper=demapper)
         self.rc = self.ctx.run_config()
         self.batch = int(batch)
         self.seed = int(seed)
@@ -154,6 +154,10 @@ def main(argv=None):
     ap.add_argument("--schedule", default=os.environ.get("KML_SCHEDULE", "flooding"), metavar="flooding|layered",
                     help="row schedule of the min-sum decodes: flooding (default) or layered (opt-in, needs "
                          "--algorithm nms; about half the iterations for the same error rate)")
+    ap.add_argument("--demapper", default=os.environ.get("KML_DEMAPPER", "exact"), metavar="exact|maxlog",
+                    help="front end of the min-sum receive path: exact (default, the reference's fp64 demapper) or "
+                         "maxlog (opt-in, needs --algorithm nms; float max-log LLRs, a 5G code's candidate metric "
+                         "decodes included)")
     ap.add_argument("--force-dist", action="store_true", default=os.environ.get("KML_FORCE_DIST", "") == "1",
                     help="build the process group (and run its all-reduces) even when WORLD_SIZE is 1, "
                          "e.g. a 1-rank RCCL group under torchrun --nproc-per-node 1")
@@ -176,11 +180,17 @@ def main(argv=None):
         ap.error("--schedule / KML_SCHEDULE must be flooding or layered")
     if args.schedule == "layered" and alg_name != "nms":
         ap.error("--schedule layered needs --algorithm nms: the schedule belongs to the min-sum mode")
+    if args.demapper not in ("exact", "maxlog"):
+        ap.error("--demapper / KML_DEMAPPER must be exact or maxlog")
+    if args.demapper == "maxlog" and alg_name != "nms":
+        ap.error("--demapper maxlog needs --algorithm nms: the max-log front end belongs to the min-sum mode")
     if alg_name == "nms":  # the first line of an nms run states the mode too
         log.info(f"BP decode algorithm: nms (normalized min-sum, alpha = {float(alg_alpha or 0.75):g}; "
                  "not the reference's decoder)")
     if args.schedule == "layered":
         log.info("BP decode schedule: layered")
+    if args.demapper == "maxlog":
+        log.info("Demapper: maxlog (max-log LLR front end; not the reference's demapper)")
     log.info("Start simulation")
     if not os.path.exists(args.config):
         log.error("Encouter error while opening config.toml")
@@ -199,7 +209,7 @@ def main(argv=None):
         dist = dist_mod
     sim = Simulator(args.config, device=local, batch=args.batch, seed=args.seed, dist=dist, log=log,
                     comm_backend=args.dist_backend, precision=args.precision, algorithm=args.algorithm,
-                    schedule=args.schedule)
+                    schedule=args.schedule, demapper=args.demapper)
     sim.Simulate()
     sim.ctx.close()
     if dist is not None:
