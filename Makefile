@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall 
 CSRC     := kmldpc_amd/csrc
 OBJDIR   := build/obj
 CPP_SRCS := config code modem layout capi context receive matfile simulate refstream comm
-HIP_SRCS := bp bp_regular bp_regular_f32 bp_irregular bp_irregular_nms bp_irregular_lnms bp_coop demap demap_llr kmeans framegen
+HIP_SRCS := bp bp_regular bp_regular_f32 bp_irregular bp_irregular_nms bp_irregular_lnms bp_irregular_lnms_h16 bp_coop demap demap_llr kmeans framegen
 OBJS     := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(CPP_SRCS) $(HIP_SRCS)))
 HDRS     := $(wildcard $(CSRC)/*.hpp) include/kmldpc_amd.h
 LIB      := kmldpc_amd/libkmldpc_amd.so

@@ -298,6 +298,57 @@ int kml_demap_llr(kml_ctx *ctx, const double *y, const double *h, double var, in
 int kml_llr_decode(kml_ctx *ctx, const float *llr, int B, int iter_count, uint8_t *uu_hat, int32_t *ret,
                    uint8_t *cc_hat, float *llr_out, int flags);
 
+/* The message format of the layered min-sum decoder, a fifth axis beside
+ * precision, algorithm, schedule and demapper.  KML_MSG_F32 (the default,
+ * always accepted): every path runs what it ran before.  KML_MSG_F16 sends
+ * every layered min-sum decode of the context to bp_irregular_lnms_h16_kernel
+ * (kmldpc_amd/csrc/bp_irregular_lnms_h16.hip), which keeps the decoder state in
+ * IEEE binary16 and decodes two codewords in the two halves of every 32-bit
+ * word.  It is held to tests/bp_h16_model.py, which the kernel equals bit for
+ * bit.
+ * The arithmetic contract is KML_SCHED_LAYERED's above with one change: every
+ * value of the decoder state is IEEE binary16, denormals kept, no fma, each
+ * operation rounded once to nearest-even.
+ *   - Prior: the float L of the existing contract rounded once to binary16: in
+ *     the P0 front end L = (float)(log q - log(1 - q)), in the LLR front end
+ *     L = min(max(x, -256.0f), 256.0f); a punctured column has +0.
+ *   - alpha: a16 = RN16((float)alpha), to float first and then to half (0.75,
+ *     0.8125 and 1 are exact).
+ *   - Sweep, the same four steps, each one binary16 operation:
+ *     m_j = clamp(T[v_j] - c2v_j, -256, 256); the magnitudes compared as the
+ *     unsigned integers their 15-bit patterns are; c2v_j = RN16(a16 * a_j) with
+ *     its sign bit set to s_j; T[v_j] = m_j + c2v_j.
+ *   - Decisions (T > 0 ? 0 : 1, a tie decides 1), the stop rule (a budget of k
+ *     uses all k sweeps), ret = it + (it < max_iter) and iter_count = 0 (outputs
+ *     as passed) are unchanged.
+ *   - llr_out of kml_llr_decode is the binary16 T widened to float, which is
+ *     exact; bit patterns, -0 and +0 differ.
+ * A codeword's result does not depend on the codeword it shares its words with,
+ * nor on the batch size or its place in the batch; ret, iters, the per-codeword
+ * outputs and the counters are each codeword's own, as the f32 kernel reports
+ * them.
+ * Scope: that of kml_set_schedule plus the LLR entry: the final decode of
+ * kml_bp_decode, kml_decode_frames, kml_decode_candidates, kml_sim_decode(_ex)
+ * and kml_sim_point; kml_llr_decode with llr_out; under KML_DEMAP_MAXLOG a 5G
+ * code's candidate metric decodes.  k-means, both demappers and the exact front
+ * end's fp64 candidate metrics are untouched.
+ * KML_MSG_F16 returns KML_E_UNSUP, and the context keeps its value, on a
+ * host-only context, with KML_BP_KERNEL=generic, and on a context that is not in
+ * KML_ALG_NMS and KML_SCHED_LAYERED (the flooding schedule has no binary16
+ * kernel).  KML_E_ARG: an unknown value; KML_MSG_F16 when the context's alpha
+ * rounds to +0 in binary16 (alpha <= 2^-25); and, in the F16 format,
+ * kml_set_algorithm(KML_ALG_NMS, alpha) with such an alpha, the context left
+ * unchanged.  kml_set_algorithm(KML_ALG_SPA) and
+ * kml_set_schedule(KML_SCHED_FLOODING) return the format to F32;
+ * kml_set_algorithm(KML_ALG_NMS, alpha), kml_set_schedule(KML_SCHED_LAYERED)
+ * and kml_set_demapper keep it.  The min-sum mode's refusals (syn, the
+ * soft-syndrome metric, kml_sim_decode_profile) hold as they are.  There is no
+ * fallback. */
+#define KML_MSG_F32 0
+#define KML_MSG_F16 1
+int kml_set_messages(kml_ctx *ctx, int fmt);
+int kml_get_messages(const kml_ctx *ctx);
+
 int kml_dims(const kml_ctx *ctx, int32_t *dims /* [KML_DIM_COUNT] */);
 /* Host-side code plan, for inspection and parity tests. */
 int kml_code_perm(const kml_ctx *ctx, int32_t *perm /* [Ncol] */);

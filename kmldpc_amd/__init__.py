@@ -34,6 +34,7 @@ PRECISIONS = {"f64": 0, "f32": 1}  # KML_PREC_F64, KML_PREC_F32
 ALGORITHMS = {"spa": 0, "nms": 1}  # KML_ALG_SPA, KML_ALG_NMS
 SCHEDULES = {"flooding": 0, "layered": 1}  # KML_SCHED_FLOODING, KML_SCHED_LAYERED
 DEMAPPERS = {"exact": 0, "maxlog": 1}  # KML_DEMAP_EXACT, KML_DEMAP_MAXLOG
+MESSAGES = {"f32": 0, "f16": 1}  # KML_MSG_F32, KML_MSG_F16
 DIM_NAMES = ["M", "Ncol", "K", "cc_len", "Z", "E", "chk", "max_iter", "bits", "Kc", "S", "bp_lds", "part_group"]
 
 
@@ -89,6 +90,8 @@ def lib():
         "kml_code_layers": (I, [P, P, I]),
         "kml_set_demapper": (I, [P, I]),
         "kml_get_demapper": (I, [P]),
+        "kml_set_messages": (I, [P, I]),
+        "kml_get_messages": (I, [P]),
         "kml_demap_llr": (I, [P, P, P, D, I, P, I]),
         "kml_llr_decode": (I, [P, P, I, I, P, P, P, P, I]),
         "kml_create": (I, [C.c_char_p, C.c_char_p, I, PP]),
@@ -181,7 +184,7 @@ class Context:
 
     def __init__(self, config=None, data_dir=None, device=0, *, matrix_file=None, modem_file=None, is5g=False,
                  active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64", algorithm="spa",
-                 schedule="flooding", demapper="exact"):
+                 schedule="flooding", demapper="exact", messages="f32"):
         L = lib()
         h = C.c_void_p()
         if config is not None:
@@ -227,6 +230,12 @@ class Context:
         if demapper != "exact":
             try:
                 self.set_demapper(demapper)
+            except Exception:
+                self.close()
+                raise
+        if messages != "f32":
+            try:
+                self.set_messages(messages)
             except Exception:
                 self.close()
                 raise
@@ -312,6 +321,19 @@ class Context:
     def demapper(self):
         v = int(lib().kml_get_demapper(self._h))
         return {n: k for k, n in DEMAPPERS.items()}[v]
+
+    # ---- message format of the layered min-sum decodes (kml_set_messages)
+    def set_messages(self, messages):
+        """"f32" (default, always accepted) or "f16" (opt-in, the layered min-sum decoder only: the decoder state
+        is IEEE binary16 and a workgroup decodes two codewords at once; its arithmetic is
+        tests/bp_h16_model.py's bit for bit).  Raises KmlError with code -4 where it is not available."""
+        # an unknown name reaches the library as an unknown value, which answers KML_E_ARG
+        self._chk(lib().kml_set_messages(self._h, MESSAGES.get(messages, -1)), f"kml_set_messages({messages!r})")
+
+    @property
+    def messages(self):
+        v = int(lib().kml_get_messages(self._h))
+        return {n: k for k, n in MESSAGES.items()}[v]
 
     def layers(self):
         """layer_ptr[nl + 1] of the layered schedule (kml_code_layers): layer l = rows [layer_ptr[l], layer_ptr[l + 1])."""

@@ -329,7 +329,7 @@ long long bp_gslots_needed(const DevCode &c) {
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family,
                      const LnmsPlanDev *lnms, const LlrIoDev *llr) {
   if (a.B <= 0) return hipSuccess;
-  if (llr && a.prec != 2 && a.prec != 3) {  // no other family reads float priors
+  if (llr && a.prec != 2 && a.prec != 3 && a.prec != 4) {  // no other family reads float priors
     if (err) *err = "the LLR front end belongs to the min-sum kernels";
     return hipErrorNotSupported;
   }
@@ -342,8 +342,9 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
     if (err) *err = "dequeue counter missing";
     return hipErrorInvalidValue;
   }
-  if (a.prec == 2 || a.prec == 3) {  // the opt-in normalized min-sum mode: its kernel or an error, never another family
-    const bool layered = a.prec == 3;  // ... in the layered schedule: bp_irregular_lnms.hip, by the same rule
+  if (a.prec == 2 || a.prec == 3 || a.prec == 4) {  // the opt-in normalized min-sum mode: its kernel or an error, never another family
+    const bool h16 = a.prec == 4;                // ... on binary16 messages: bp_irregular_lnms_h16.hip, layered only
+    const bool layered = a.prec == 3 || h16;     // ... in the layered schedule: bp_irregular_lnms.hip, by the same rule
     const char *why = nullptr;
     if (a.cw_prof || a.prof) why = "the iteration profile is not available in the min-sum mode (a follow-up)";
     if (a.syn) why = "the min-sum decoder has no syndrom_soft: syn must be NULL";
@@ -361,17 +362,21 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
       return hipErrorNotSupported;
     }
     hipError_t e;
-    if (llr)
+    if (h16)
+      e = launch_bp_irregular_lnms_h16(c, a, *lnms, llr, s);
+    else if (llr)
       e = layered ? launch_bp_irregular_lnms(c, a, *lnms, *llr, s) : launch_bp_irregular_nms(c, a, *llr, s);
     else
       e = layered ? launch_bp_irregular_lnms(c, a, *lnms, s) : launch_bp_irregular_nms(c, a, s);
     if (e == hipErrorNotSupported) {
       if (err)
-        *err = layered ? "the layered min-sum BP kernel does not take this code or launch"
-                       : "the min-sum BP kernel does not take this code or launch";
+        *err = h16       ? "the binary16 layered min-sum BP kernel does not take this code or launch"
+               : layered ? "the layered min-sum BP kernel does not take this code or launch"
+                         : "the min-sum BP kernel does not take this code or launch";
       return e;
     }
-    if (family) *family = layered ? "bp_irregular_lnms_kernel" : "bp_irregular_nms_kernel";
+    if (family)
+      *family = h16 ? "bp_irregular_lnms_h16_kernel" : layered ? "bp_irregular_lnms_kernel" : "bp_irregular_nms_kernel";
     return e;
   }
   if (a.prec != 0) {  // the opt-in single-precision mode: its kernel or an error, never another family

@@ -22,6 +22,9 @@ int host_chunk() {
   return 8192;
 }
 
+// Does RN16(a) give +0 for this a > 0?  (Half of binary16's smallest denormal, 2^-25, ties to even: zero.)
+bool half_rounds_to_zero(float a) { return a <= 0x1p-25f; }
+
 const double2 *as_c(const double *p) { return reinterpret_cast<const double2 *>(p); }
 double2 *as_c(double *p) { return reinterpret_cast<double2 *>(p); }
 
@@ -184,6 +187,7 @@ int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
     c->algorithm = alg;
     c->schedule = KML_SCHED_FLOODING;
     c->demapper = KML_DEMAP_EXACT;  // ... and so does the max-log front end
+    c->messages = KML_MSG_F32;      // ... and the binary16 message format
     return KML_OK;
   }
   if (alpha == 0.0) alpha = 0.75;
@@ -192,6 +196,9 @@ int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
   const float af = (float)alpha;
   if (!(af > 0.0f))
     return fail(c, KML_E_ARG, "kml_set_algorithm: alpha rounds to zero in single precision");
+  if (c->messages == KML_MSG_F16 && half_rounds_to_zero(af))
+    return fail(c, KML_E_ARG,
+                "kml_set_algorithm: alpha rounds to zero in binary16 (KML_MSG_F16); the context keeps its algorithm");
   if (c->device < 0 || !c->stream)
     return fail(c, KML_E_UNSUP, "kml_set_algorithm: a host-only context (device < 0) has no min-sum decoder");
   if (c->precision != KML_PREC_F64)
@@ -218,8 +225,9 @@ int kml_set_schedule(kml_ctx *c, int sched) {
   call_begin(c);
   if (sched != KML_SCHED_FLOODING && sched != KML_SCHED_LAYERED)
     return fail(c, KML_E_ARG, "kml_set_schedule: unknown schedule " + std::to_string(sched));
-  if (sched == KML_SCHED_FLOODING) {  // always accepted
+  if (sched == KML_SCHED_FLOODING) {  // always accepted; the binary16 format belongs to the layered schedule
     c->schedule = sched;
+    c->messages = KML_MSG_F32;
     return KML_OK;
   }
   if (c->device < 0 || !c->stream)
@@ -269,6 +277,32 @@ int kml_set_demapper(kml_ctx *c, int demapper) {
 }
 
 int kml_get_demapper(const kml_ctx *c) { return c ? c->demapper : KML_E_ARG; }
+
+int kml_set_messages(kml_ctx *c, int fmt) {
+  if (!c) return KML_E_ARG;
+  call_begin(c);
+  if (fmt != KML_MSG_F32 && fmt != KML_MSG_F16)
+    return fail(c, KML_E_ARG, "kml_set_messages: unknown message format " + std::to_string(fmt));
+  if (fmt == KML_MSG_F32) {  // always accepted
+    c->messages = fmt;
+    return KML_OK;
+  }
+  if (c->device < 0 || !c->stream)
+    return fail(c, KML_E_UNSUP, "kml_set_messages: a host-only context (device < 0) has no min-sum decoder");
+  if (kml::bp_generic_forced())
+    return fail(c, KML_E_UNSUP, "kml_set_messages: the binary16 format is not available with KML_BP_KERNEL=generic");
+  if (c->algorithm != KML_ALG_NMS || c->schedule != KML_SCHED_LAYERED)
+    return fail(c, KML_E_UNSUP,
+                "kml_set_messages: the binary16 format belongs to the layered min-sum decoder "
+                "(kml_set_algorithm(KML_ALG_NMS) and kml_set_schedule(KML_SCHED_LAYERED) first; the flooding schedule "
+                "has no binary16 kernel); the context keeps its format");
+  if (half_rounds_to_zero(c->nms_alpha))
+    return fail(c, KML_E_ARG, "kml_set_messages: the context's alpha rounds to zero in binary16");
+  c->messages = fmt;
+  return KML_OK;
+}
+
+int kml_get_messages(const kml_ctx *c) { return c ? c->messages : KML_E_ARG; }
 
 int kml_dims(const kml_ctx *c, int32_t *d) {
   if (!c || !d) return KML_E_ARG;

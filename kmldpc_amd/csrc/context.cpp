@@ -332,7 +332,7 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric, c
   a.prec = metric ? KML_PREC_F64 : c->precision;
   if (!metric && c->algorithm == KML_ALG_NMS) {  // (never with the f32 precision: kml_set_algorithm)
     if (a.syn) return fail(c, KML_E_UNSUP, "the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
-    a.prec = c->schedule == KML_SCHED_LAYERED ? 3 : 2;
+    a.prec = c->schedule == KML_SCHED_LAYERED ? (c->messages == KML_MSG_F16 ? 4 : 3) : 2;
     a.nms_alpha = c->nms_alpha;
   }
   int slot = reuse;

@@ -108,7 +108,9 @@ struct BpLaunch {
   // other code, there is no fallback in either direction); 2: the normalized
   // min-sum kernel (bp_irregular_nms.hip, the codes of bp_irregular.hip only,
   // nms_alpha above; the same rule); 3: its layered schedule
-  // (bp_irregular_lnms.hip, the same codes, nms_alpha, launch_bp's lnms plan)
+  // (bp_irregular_lnms.hip, the same codes, nms_alpha, launch_bp's lnms plan);
+  // 4: the layered schedule on binary16 messages (bp_irregular_lnms_h16.hip,
+  // the same codes, plan and rule)
   int prec = 0;
   // Iteration profile (bp_regular.hip / bp_irregular.hip only, SYN = false,
   // ref_bits set, 1 <= iter_count <= kBpProfMaxIter): when either is set the
@@ -173,6 +175,13 @@ bool bp_irregular_nms_post_supported(const DevCode &c);
 hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, hipStream_t s);
 hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev &io,
                                     hipStream_t s);
+// The binary16 message format of the layered kernel (BpLaunch::prec = 4,
+// bp_irregular_lnms_h16.hip): the codes, the layer plan and the launch rules of
+// launch_bp_irregular_lnms; two codewords a workgroup, one in each half of a
+// 32-bit word.  io = NULL: P0 priors; else float priors (and posteriors out
+// when io->post is set), as above.
+hipError_t launch_bp_irregular_lnms_h16(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp,
+                                        const LlrIoDev *io, hipStream_t s);
 // KML_BP_KERNEL=generic (read now, and as the dispatch first read it).
 bool bp_generic_forced();
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of

@@ -25,7 +25,10 @@
 // kml_set_schedule; layered needs nms and states itself in the line after the
 // algorithm's), KML_DEMAPPER (exact or maxlog, also `--demapper exact|maxlog`:
 // the front end of the min-sum receive path, kml_set_demapper; maxlog needs nms
-// and states itself in the line after the schedule's).
+// and states itself in the line after the schedule's), KML_MESSAGES (f32 or f16,
+// also `--messages f32|f16`: the message format of the layered min-sum decodes,
+// kml_set_messages; f16 needs nms and layered and states itself in the line
+// after the demapper's).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -106,6 +109,7 @@ int main(int argc, char **argv) {
   std::string alg = getenv("KML_ALGORITHM") ? getenv("KML_ALGORITHM") : "spa";
   std::string sched = getenv("KML_SCHEDULE") ? getenv("KML_SCHEDULE") : "flooding";
   std::string demapper = getenv("KML_DEMAPPER") ? getenv("KML_DEMAPPER") : "exact";
+  std::string messages = getenv("KML_MESSAGES") ? getenv("KML_MESSAGES") : "f32";
   for (int i = 1; i < argc; i++) {
     const std::string arg = argv[i];
     if (arg == "--precision" && i + 1 < argc)
@@ -124,6 +128,10 @@ int main(int argc, char **argv) {
       demapper = argv[++i];
     else if (arg.rfind("--demapper=", 0) == 0)
       demapper = arg.substr(11);
+    else if (arg == "--messages" && i + 1 < argc)
+      messages = argv[++i];
+    else if (arg.rfind("--messages=", 0) == 0)
+      messages = arg.substr(11);
     else
       cfg = arg;
   }
@@ -160,12 +168,22 @@ int main(int argc, char **argv) {
     error("--demapper maxlog needs --algorithm nms: the max-log front end belongs to the min-sum mode");
     return 255;
   }
+  if (messages != "f32" && messages != "f16") {
+    error("--messages / KML_MESSAGES must be f32 or f16");
+    return 255;
+  }
+  if (messages == "f16" && !(alg == "nms" && sched == "layered")) {
+    error("--messages f16 needs --algorithm nms --schedule layered: the binary16 format belongs to the layered "
+          "min-sum decoder");
+    return 255;
+  }
   if (prec == "f32") info("BP decode precision: f32 (single precision, not bit-exact with the reference)");
   if (alg == "nms")
     info(fmt("BP decode algorithm: nms (normalized min-sum, alpha = %g; not the reference's decoder)",
              alpha > 0.0 ? (double)(float)alpha : 0.75));
   if (sched == "layered") info("BP decode schedule: layered");
   if (demapper == "maxlog") info("Demapper: maxlog (max-log LLR front end; not the reference's demapper)");
+  if (messages == "f16") info("BP message format: f16 (binary16 decoder state; two codewords a workgroup)");
   info("Start simulation");
   {
     FILE *f = fopen(cfg.c_str(), "rb");
@@ -201,6 +219,11 @@ int main(int argc, char **argv) {
     return 255;
   }
   if (demapper == "maxlog" && kml_set_demapper(ctx, KML_DEMAP_MAXLOG) != KML_OK) {
+    error(kml_last_error(ctx));
+    kml_destroy(ctx);
+    return 255;
+  }
+  if (messages == "f16" && kml_set_messages(ctx, KML_MSG_F16) != KML_OK) {
     error(kml_last_error(ctx));
     kml_destroy(ctx);
     return 255;

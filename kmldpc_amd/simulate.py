@@ -76,10 +76,11 @@ class Simulator:
     """Simulator (include/simulator.h): constructed from config.toml, Simulate() runs the sweep."""
 
     def __init__(self, config, data_dir=None, device=0, batch=32768, seed=0, dist=None, log=None, comm_backend="nccl",
-                 precision="f64", algorithm="spa", schedule="flooding", demapper="exact"):
+                 precision="f64", algorithm="spa", schedule="flooding", demapper="exact", messages="f32"):
         self.log = log or Logger(enabled=(dist.get_rank() if dist else 0) == 0)
         self.ctx = Context(config, data_dir=data_dir or os.path.dirname(os.path.abspath(config)), device=device,
-                           precision=precision, algorithm=algorithm, schedule=schedule, demapper=demapper)
+                           precision=precision, algorithm=algorithm, schedule=schedule, demapper=demapper,
+                           messages=messages)
         self.rc = self.ctx.run_config()
         self.batch = int(batch)
         self.seed = int(seed)
@@ -158,6 +159,9 @@ def main(argv=None):
                     help="front end of the min-sum receive path: exact (default, the reference's fp64 demapper) or "
                          "maxlog (opt-in, needs --algorithm nms; float max-log LLRs, a 5G code's candidate metric "
                          "decodes included)")
+    ap.add_argument("--messages", default=os.environ.get("KML_MESSAGES", "f32"), metavar="f32|f16",
+                    help="message format of the layered min-sum decodes: f32 (default) or f16 (opt-in, needs "
+                         "--algorithm nms --schedule layered; binary16 state, two codewords a workgroup)")
     ap.add_argument("--force-dist", action="store_true", default=os.environ.get("KML_FORCE_DIST", "") == "1",
                     help="build the process group (and run its all-reduces) even when WORLD_SIZE is 1, "
                          "e.g. a 1-rank RCCL group under torchrun --nproc-per-node 1")
@@ -184,6 +188,11 @@ def main(argv=None):
         ap.error("--demapper / KML_DEMAPPER must be exact or maxlog")
     if args.demapper == "maxlog" and alg_name != "nms":
         ap.error("--demapper maxlog needs --algorithm nms: the max-log front end belongs to the min-sum mode")
+    if args.messages not in ("f32", "f16"):
+        ap.error("--messages / KML_MESSAGES must be f32 or f16")
+    if args.messages == "f16" and not (alg_name == "nms" and args.schedule == "layered"):
+        ap.error("--messages f16 needs --algorithm nms --schedule layered: the binary16 format belongs to the "
+                 "layered min-sum decoder")
     if alg_name == "nms":  # the first line of an nms run states the mode too
         log.info(f"BP decode algorithm: nms (normalized min-sum, alpha = {float(alg_alpha or 0.75):g}; "
                  "not the reference's decoder)")
@@ -191,6 +200,8 @@ def main(argv=None):
         log.info("BP decode schedule: layered")
     if args.demapper == "maxlog":
         log.info("Demapper: maxlog (max-log LLR front end; not the reference's demapper)")
+    if args.messages == "f16":
+        log.info("BP message format: f16 (binary16 decoder state; two codewords a workgroup)")
     log.info("Start simulation")
     if not os.path.exists(args.config):
         log.error("Encouter error while opening config.toml")
@@ -209,7 +220,7 @@ def main(argv=None):
         dist = dist_mod
     sim = Simulator(args.config, device=local, batch=args.batch, seed=args.seed, dist=dist, log=log,
                     comm_backend=args.dist_backend, precision=args.precision, algorithm=args.algorithm,
-                    schedule=args.schedule, demapper=args.demapper)
+                    schedule=args.schedule, demapper=args.demapper, messages=args.messages)
     sim.Simulate()
     sim.ctx.close()
     if dist is not None:
