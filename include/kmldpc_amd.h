@@ -349,6 +349,43 @@ int kml_llr_decode(kml_ctx *ctx, const float *llr, int B, int iter_count, uint8_
 int kml_set_messages(kml_ctx *ctx, int fmt);
 int kml_get_messages(const kml_ctx *ctx);
 
+/* The offset correction of the min-sum check-node rule, a sixth axis beside
+ * precision, algorithm, schedule, demapper and message format.  beta = 0 (the
+ * default, always accepted, on host-only contexts too): every path runs what it
+ * ran before, on the kernel instances it ran before.  beta > 0 sends every
+ * min-sum decode of the context (flooding, layered, layered binary16) to the
+ * offset instances of its kernel; kml_bp_kernel keeps naming the three families.
+ * They are held to tests/bp_oms_model.py, which they equal bit for bit.
+ * The arithmetic contract is that of the context's min-sum decoder with two
+ * more operations in every check-node update.  Flooding and layered f32 (IEEE
+ * binary32, denormals kept, no fma), b = (float)beta:
+ *     c = RN(alpha * a_j);  c = RN(c - b), one rounding;  c = c > 0 ? c : +0;
+ *     then the sign bit of c is set to s_j, exactly as without the offset.
+ * Layered binary16: the same in binary16 with b16 = RN16((float)beta): a packed
+ * multiply, a packed subtract, a packed max with +0.  No -0 reaches the max:
+ * x - x is +0 in round-to-nearest and alpha * a_j is never negative, so the
+ * operand of the max is positive, negative or +0.
+ *   - A message of magnitude zero with its sign bit set (-0) is legal and is
+ *     covered by the existing rules: -0 counts as negative in the sign XOR of
+ *     m, and m + (-0) = m.
+ *   - Priors, the +-256 clamp, the tie rule, the stop rule, ret and the counters
+ *     are unchanged.
+ * Scope: wherever the context's min-sum decoder runs, a 5G code's candidate
+ * metric decodes under KML_DEMAP_MAXLOG included; under the exact demapper those
+ * metric decodes stay fp64 sum-product.
+ * KML_E_ARG: beta negative, NaN, infinite or > 256; a positive beta that rounds
+ * to +0 in float; in the F16 format a positive beta that rounds to +0 in
+ * binary16 (beta <= 2^-25), and kml_set_messages(KML_MSG_F16) when the
+ * context's beta does.  beta > 0 returns KML_E_UNSUP, and the context keeps its
+ * value, on a host-only context, on a context that is not in KML_ALG_NMS, and
+ * with KML_BP_KERNEL=generic.  kml_set_algorithm(KML_ALG_SPA) returns the offset
+ * to 0; kml_set_algorithm(KML_ALG_NMS, alpha), kml_set_schedule,
+ * kml_set_demapper and kml_set_messages keep it.  The min-sum mode's refusals
+ * (syn, the soft-syndrome metric, kml_sim_decode_profile) hold as they are.
+ * There is no fallback.  KML_ABI_VERSION stays 2. */
+int kml_set_nms_offset(kml_ctx *ctx, double beta);
+int kml_get_nms_offset(const kml_ctx *ctx, double *beta);
+
 int kml_dims(const kml_ctx *ctx, int32_t *dims /* [KML_DIM_COUNT] */);
 /* Host-side code plan, for inspection and parity tests. */
 int kml_code_perm(const kml_ctx *ctx, int32_t *perm /* [Ncol] */);

@@ -92,6 +92,8 @@ def lib():
         "kml_get_demapper": (I, [P]),
         "kml_set_messages": (I, [P, I]),
         "kml_get_messages": (I, [P]),
+        "kml_set_nms_offset": (I, [P, D]),
+        "kml_get_nms_offset": (I, [P, P]),
         "kml_demap_llr": (I, [P, P, P, D, I, P, I]),
         "kml_llr_decode": (I, [P, P, I, I, P, P, P, P, I]),
         "kml_create": (I, [C.c_char_p, C.c_char_p, I, PP]),
@@ -184,7 +186,7 @@ class Context:
 
     def __init__(self, config=None, data_dir=None, device=0, *, matrix_file=None, modem_file=None, is5g=False,
                  active=True, max_iter=20, metric_soft=False, metric_iter=5, precision="f64", algorithm="spa",
-                 schedule="flooding", demapper="exact", messages="f32"):
+                 schedule="flooding", demapper="exact", messages="f32", offset=0.0):
         L = lib()
         h = C.c_void_p()
         if config is not None:
@@ -236,6 +238,12 @@ class Context:
         if messages != "f32":
             try:
                 self.set_messages(messages)
+            except Exception:
+                self.close()
+                raise
+        if offset != 0.0:
+            try:
+                self.set_offset(offset)
             except Exception:
                 self.close()
                 raise
@@ -334,6 +342,21 @@ class Context:
     def messages(self):
         v = int(lib().kml_get_messages(self._h))
         return {n: k for k, n in MESSAGES.items()}[v]
+
+    # ---- offset correction of the min-sum check-node rule (kml_set_nms_offset)
+    def set_offset(self, beta):
+        """0 (default, always accepted) or beta in (0, 256] (opt-in, the min-sum mode only: every check-node
+        message becomes max(alpha * a - beta, +0) ahead of its sign, in the flooding, layered and binary16
+        decoders; its arithmetic is tests/bp_oms_model.py's bit for bit).  Raises KmlError with code -4 where
+        it is not available."""
+        self._chk(lib().kml_set_nms_offset(self._h, float(beta)), f"kml_set_nms_offset({beta!r})")
+
+    @property
+    def offset(self):
+        """beta as the library holds it (a float32 value)."""
+        b = C.c_double(0.0)
+        self._chk(lib().kml_get_nms_offset(self._h, C.byref(b)), "kml_get_nms_offset")
+        return b.value
 
     def layers(self):
         """layer_ptr[nl + 1] of the layered schedule (kml_code_layers): layer l = rows [layer_ptr[l], layer_ptr[l + 1])."""

@@ -327,8 +327,12 @@ long long bp_gslots_needed(const DevCode &c) {
 }
 
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family,
-                     const LnmsPlanDev *lnms, const LlrIoDev *llr) {
+                     const LnmsPlanDev *lnms, const LlrIoDev *llr, const OmsDev *oms) {
   if (a.B <= 0) return hipSuccess;
+  if (oms && a.prec != 2 && a.prec != 3 && a.prec != 4) {  // no other family has a min-sum CN rule
+    if (err) *err = "the offset correction belongs to the min-sum kernels";
+    return hipErrorNotSupported;
+  }
   if (llr && a.prec != 2 && a.prec != 3 && a.prec != 4) {  // no other family reads float priors
     if (err) *err = "the LLR front end belongs to the min-sum kernels";
     return hipErrorNotSupported;
@@ -362,12 +366,11 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
       return hipErrorNotSupported;
     }
     hipError_t e;
+    // (the offset only picks the instance: the routing on prec is as it was)
     if (h16)
-      e = launch_bp_irregular_lnms_h16(c, a, *lnms, llr, s);
-    else if (llr)
-      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, *llr, s) : launch_bp_irregular_nms(c, a, *llr, s);
+      e = launch_bp_irregular_lnms_h16(c, a, *lnms, llr, oms, s);
     else
-      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, s) : launch_bp_irregular_nms(c, a, s);
+      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, llr, oms, s) : launch_bp_irregular_nms(c, a, llr, oms, s);
     if (e == hipErrorNotSupported) {
       if (err)
         *err = h16       ? "the binary16 layered min-sum BP kernel does not take this code or launch"

@@ -45,6 +45,11 @@
 // LDS: T (N floats), c2v (E floats), the pass words, 16 bytes of tallies, the
 // column of every edge and the row pointers as u16, N decision bytes: 59.5 KB
 // for BG2, so two workgroups share a CU.
+//
+// The offset instances (kml_set_nms_offset, kernels.hpp OmsDev) put two more
+// operations behind the multiply: c = RN(c - beta), c = c > 0 ? c : +0, ahead of
+// the sign; tests/bp_oms_model.py states them and equals this file's contract at
+// beta = 0.  A context with offset 0 launches the instances without them.
 #include "bp_common.hpp"
 #include "bp_launch.hpp"
 #include "exact_math.hpp"
@@ -104,8 +109,10 @@ __device__ __forceinline__ LnmsItem lnms_item(const LnmsLds &s, int first, int n
   return it;
 }
 
-// One pass of a sweep, eight lanes a row.
-__device__ __forceinline__ void lnms_pass(const LnmsLds &s, const LnmsItem &it, float alpha) {
+// One pass of a sweep, eight lanes a row.  OMS: the offset correction
+// (kernels.hpp OmsDev), c = max(RN(c - beta), +0) ahead of the sign.
+template <bool OMS>
+__device__ __forceinline__ void lnms_pass(const LnmsLds &s, const LnmsItem &it, float alpha, float beta) {
   const int v0 = (int)(it.vv & 0xFFFFu), v1 = (int)(it.vv >> 16), e0 = it.e0, e1 = it.e0 + kLanes;
   const bool h0 = (unsigned)v0 != kNoCol, h1 = (unsigned)v1 != kNoCol;
   unsigned m0 = kInfBits, m1 = kInfBits;  // (an absent edge: above every magnitude, sign clear)
@@ -119,13 +126,15 @@ __device__ __forceinline__ void lnms_pass(const LnmsLds &s, const LnmsItem &it, 
   row_step<0x141>(x1, min2);  // row_half_mirror: lane -> 7 - lane, the other quad
   const unsigned r1 = x1 & ~kSignBit, r2 = min2, rsgn = x1 & kSignBit;
   if (h0) {
-    const float q = alpha * __int_as_float((int)(a0 == r1 ? r2 : r1));
+    float q = alpha * __int_as_float((int)(a0 == r1 ? r2 : r1));
+    if constexpr (OMS) q = fmaxf(q - beta, 0.0f);  // (q - beta is never -0 and never NaN)
     const int cb = (int)((unsigned)__float_as_int(q) | ((m0 ^ rsgn) & kSignBit));
     s.c2v[e0] = cb;
     s.post[v0] = __int_as_float((int)m0) + __int_as_float(cb);
   }
   if (h1) {
-    const float q = alpha * __int_as_float((int)(a1 == r1 ? r2 : r1));
+    float q = alpha * __int_as_float((int)(a1 == r1 ? r2 : r1));
+    if constexpr (OMS) q = fmaxf(q - beta, 0.0f);
     const int cb = (int)((unsigned)__float_as_int(q) | ((m1 ^ rsgn) & kSignBit));
     s.c2v[e1] = cb;
     s.post[v1] = __int_as_float((int)m1) + __int_as_float(cb);
@@ -163,17 +172,15 @@ __device__ __forceinline__ bool lnms_parity_fail(const LnmsLds &s, int M, int g,
 // Six waves per SIMD = two workgroups of 12 waves per CU.
 constexpr int kCachePasses = 12;
 
-// The LLR instances' extra kernel argument (none: the P0 instances).
-__device__ __forceinline__ const LlrIoDev &llr_io(const LlrIoDev &io) { return io; }
-
 // The instances without Llr are the P0 front end (the contract above).  With
 // one LlrIoDev argument the priors are the caller's floats, clamped to +-256
 // (there is no log in those instances), and POST also writes T, as the loop
-// left it, out with the decisions taken from it.
-template <int T, bool CACHED, bool POST = false, class... Llr>
+// left it, out with the decisions taken from it.  With an OmsDev argument (the
+// last one) the sweep applies the offset correction.
+template <int T, bool CACHED, bool POST = false, class... X>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void bp_irregular_lnms_kernel(
-    DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, Llr... io) {
-  constexpr bool LLR = sizeof...(Llr) > 0;
+    DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, X... io) {
+  constexpr bool LLR = pack_has<LlrIoDev, X...>, OMS = pack_has<OmsDev, X...>;
   static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -192,6 +199,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
   for (int p = tid; p < lp.npass; p += T) pass[p] = lp.pass[p];
   const LnmsLds s{post, c2v, pass, cols, rowp};
   const float alpha = a.nms_alpha;
+  float beta = 0.0f;
+  if constexpr (OMS) beta = pack_get<OmsDev>(io...).beta;
 
   const int B = a.B_dev ? (int)*a.B_dev : a.B;
   for (;;) {
@@ -206,7 +215,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
     if (entry >= B) break;
     const int cw = a.cw_idx ? a.cw_idx[entry] : entry;
     if constexpr (LLR) {
-      const float *in = llr_io(io...).llr + (long long)cw * a.p0_stride;
+      const float *in = pack_get<LlrIoDev>(io...).llr + (long long)cw * a.p0_stride;
       if (a.p0_sel) in += (long long)a.p0_sel[cw] * a.p0_sel_stride;
       for (int v = tid; v < c.N; v += T)  // (a punctured column: +0)
         post[v] = v >= c.punct ? fminf(fmaxf(in[v - c.punct], -kNmsClamp), kNmsClamp) : 0.0f;
@@ -261,13 +270,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
 #pragma unroll
         for (int p = 0; p < kCachePasses; ++p)
           if (p < lp.npass) {
-            lnms_pass(s, item[p], alpha);
+            lnms_pass<OMS>(s, item[p], alpha, beta);
             if (last >> p & 1) __syncthreads();  // the layer is complete: the next one reads its posteriors
           }
       } else {
         for (int p = 0; p < lp.npass; ++p) {
           const int w = __builtin_amdgcn_readfirstlane(pass[p]);
-          lnms_pass(s, lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l), alpha);
+          lnms_pass<OMS>(s, lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l), alpha, beta);
           if (w >> 24) __syncthreads();
         }
       }
@@ -286,7 +295,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
         for (int v = tid; v < c.N; v += T) o[v] = cch[v];
       }
       if constexpr (POST) {  // the posteriors hard was taken from
-        float *o = llr_io(io...).post + (long long)cw * c.N;
+        float *o = pack_get<LlrIoDev>(io...).post + (long long)cw * c.N;
         for (int v = tid; v < c.N; v += T) o[v] = post[v];
       }
       if (a.parity_cnt) {  // ParityCheck(cc_hat) (:281-300)
@@ -349,34 +358,29 @@ int lnms_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp
 }
 }  // namespace
 
-hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, hipStream_t s) {
+// io = NULL: P0 priors; else float priors (io->llr), and the posterior instances
+// when io->post is set.  oms: the offset instances (beta > 0), else the plain ones.
+hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev *io,
+                                    const OmsDev *oms, hipStream_t s) {
   constexpr int T = kIrrThreads;
   static_assert(T / kLanes == kLayRowsPerPass, "the plan's passes are this kernel's");
   size_t lds = 0;
   const int per_cu = lnms_launch_shape(c, a, lp, lds);
-  if (!per_cu) return hipErrorNotSupported;
-  if (lp.npass <= kCachePasses)
-    return launch_persistent(bp_irregular_lnms_kernel<T, true>, T, lds, per_cu, kNoGridCap, false, a, s, c, a,
-                             a.queue, lp);
-  return launch_persistent(bp_irregular_lnms_kernel<T, false>, T, lds, per_cu, kNoGridCap, false, a, s, c, a,
-                           a.queue, lp);
-}
-
-// The LLR front end: float priors (io.llr), and the posterior instances when io.post is set.
-hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev &io,
-                                    hipStream_t s) {
-  constexpr int T = kIrrThreads;
-  size_t lds = 0;
-  const int per_cu = lnms_launch_shape(c, a, lp, lds);
-  if (!per_cu || !io.llr) return hipErrorNotSupported;
-  auto go = [&](auto kern) {
-    return launch_persistent(kern, T, lds, per_cu, kNoGridCap, false, a, s, c, a, a.queue, lp, io);
+  if (!per_cu || (io && !io->llr)) return hipErrorNotSupported;
+  if (oms && !(oms->beta > 0.0f)) oms = nullptr;
+  auto go = [&](auto kern, const auto &...x) {
+    return launch_persistent(kern, T, lds, per_cu, kNoGridCap, false, a, s, c, a, a.queue, lp, x...);
   };
-  if (lp.npass <= kCachePasses)
-    return io.post ? go(bp_irregular_lnms_kernel<T, true, true, LlrIoDev>)
-                   : go(bp_irregular_lnms_kernel<T, true, false, LlrIoDev>);
-  return io.post ? go(bp_irregular_lnms_kernel<T, false, true, LlrIoDev>)
-                 : go(bp_irregular_lnms_kernel<T, false, false, LlrIoDev>);
+  auto pick = [&](auto cached) {
+    constexpr bool C = decltype(cached)::value;
+    if (!io) return oms ? go(bp_irregular_lnms_kernel<T, C, false, OmsDev>, *oms) : go(bp_irregular_lnms_kernel<T, C>);
+    if (io->post)
+      return oms ? go(bp_irregular_lnms_kernel<T, C, true, LlrIoDev, OmsDev>, *io, *oms)
+                 : go(bp_irregular_lnms_kernel<T, C, true, LlrIoDev>, *io);
+    return oms ? go(bp_irregular_lnms_kernel<T, C, false, LlrIoDev, OmsDev>, *io, *oms)
+               : go(bp_irregular_lnms_kernel<T, C, false, LlrIoDev>, *io);
+  };
+  return lp.npass <= kCachePasses ? pick(std::true_type{}) : pick(std::false_type{});
 }
 
 }  // namespace kml

@@ -39,6 +39,11 @@
 // the footprint is the f32 kernel's, 59.5 KB for BG2, two workgroups a CU.
 // An odd batch leaves the last pair with one live half; the dead one starts
 // recorded, with priors +0, writes nothing and counts nothing.
+//
+// The offset instances (kml_set_nms_offset, kernels.hpp OmsDev) put two more
+// operations behind the multiply: c = RN16(c - b16), b16 = RN16(beta), c = c > 0 ? c : +0, ahead of
+// the sign; tests/bp_oms_model.py states them and equals this file's contract at
+// beta = 0.  A context with offset 0 launches the instances without them.
 #include "bp_common.hpp"
 #include "bp_launch.hpp"
 #include "exact_math.hpp"
@@ -125,8 +130,22 @@ __device__ __forceinline__ LnmsItem lnms_item(const LnmsLds &s, int first, int n
   return it;
 }
 
+// c2v magnitudes of both halves: RN16(alpha * a), and with OMS the offset
+// correction (kernels.hpp OmsDev) in binary16: a packed subtract, then a packed
+// max with +0 (its operand is never -0: x - x is +0 in round-to-nearest).
+template <bool OMS>
+__device__ __forceinline__ unsigned pk_c2v(h2 alpha, h2 beta, unsigned a) {
+  h2 q = alpha * as_h2(a);
+  if constexpr (OMS) {
+    const h2 zero = {(_Float16)0.0f, (_Float16)0.0f};
+    q = __builtin_elementwise_max(q - beta, zero);
+  }
+  return as_u(q);
+}
+
 // One pass of a sweep, eight lanes a row, two codewords a lane.
-__device__ __forceinline__ void lnms_pass(const LnmsLds &s, const LnmsItem &it, h2 alpha) {
+template <bool OMS>
+__device__ __forceinline__ void lnms_pass(const LnmsLds &s, const LnmsItem &it, h2 alpha, h2 beta) {
   const int v0 = (int)(it.vv & 0xFFFFu), v1 = (int)(it.vv >> 16), e0 = it.e0, e1 = it.e0 + kLanes;
   const bool h0 = (unsigned)v0 != kNoCol, h1 = (unsigned)v1 != kNoCol;
   unsigned m0 = kInf2, m1 = kInf2;  // (an absent edge: above every magnitude, signs clear)
@@ -140,13 +159,13 @@ __device__ __forceinline__ void lnms_pass(const LnmsLds &s, const LnmsItem &it, 
   row_step<0x141>(x1, min2);  // row_half_mirror: lane -> 7 - lane, the other quad
   const unsigned r2 = min2, rsgn = x1 & kSign2, rsum = pk_add(x1 & ~kSign2, r2);
   if (h0) {
-    const unsigned q = as_u(alpha * as_h2(pk_sub(rsum, pk_min(a0, r2))));  // min2 where a0 holds min1, min1 elsewhere
+    const unsigned q = pk_c2v<OMS>(alpha, beta, pk_sub(rsum, pk_min(a0, r2)));  // min2 where a0 holds min1, min1 elsewhere
     const unsigned cb = q | ((m0 ^ rsgn) & kSign2);
     s.c2v[e0] = cb;
     s.post[v0] = as_u(as_h2(m0) + as_h2(cb));
   }
   if (h1) {
-    const unsigned q = as_u(alpha * as_h2(pk_sub(rsum, pk_min(a1, r2))));
+    const unsigned q = pk_c2v<OMS>(alpha, beta, pk_sub(rsum, pk_min(a1, r2)));
     const unsigned cb = q | ((m1 ^ rsgn) & kSign2);
     s.c2v[e1] = cb;
     s.post[v1] = as_u(as_h2(m1) + as_h2(cb));
@@ -181,12 +200,10 @@ __device__ __forceinline__ unsigned lnms_odd_rows(const LnmsLds &s, const LnmsIt
 
 constexpr int kCachePasses = 12;  // as in bp_irregular_lnms.hip: BG2's passes live in registers
 
-__device__ __forceinline__ const LlrIoDev &llr_io(const LlrIoDev &io) { return io; }
-
 // What a recorded half reports (the f32 kernel's epilogue, from half H of T).
-template <int T, int H, bool POST, class... Llr>
+template <int T, int H, bool POST, class... X>
 __device__ __forceinline__ void lnms_record(const DevCode &c, const BpLaunch &a, const LnmsLds &s, unsigned char *cch,
-                                            int *red, int cw, int iter, bool conv, int tid, const Llr &...io) {
+                                            int *red, int cw, int iter, bool conv, int tid, const X &...io) {
   if (a.iter_count > 0) {
     for (int v = tid; v < c.N; v += T) cch[v] = (unsigned char)hard_of<H>(s.post[v]);
     __syncthreads();
@@ -199,7 +216,7 @@ __device__ __forceinline__ void lnms_record(const DevCode &c, const BpLaunch &a,
       for (int v = tid; v < c.N; v += T) o[v] = cch[v];
     }
     if constexpr (POST) {  // the posteriors hard was taken from, widened
-      float *o = llr_io(io...).post + (long long)cw * c.N;
+      float *o = pack_get<LlrIoDev>(io...).post + (long long)cw * c.N;
       for (int v = tid; v < c.N; v += T) o[v] = half_of<H>(s.post[v]);
     }
     if (a.parity_cnt) {
@@ -243,10 +260,10 @@ __device__ __forceinline__ void lnms_record(const DevCode &c, const BpLaunch &a,
 }
 
 // The float prior of column v >= punct of one codeword, before the rounding to half.
-template <bool LLR, class... Llr>
-__device__ __forceinline__ const void *prior_row(const BpLaunch &a, int cw, const Llr &...io) {
+template <bool LLR, class... X>
+__device__ __forceinline__ const void *prior_row(const BpLaunch &a, int cw, const X &...io) {
   if constexpr (LLR) {
-    const float *in = llr_io(io...).llr + (long long)cw * a.p0_stride;
+    const float *in = pack_get<LlrIoDev>(io...).llr + (long long)cw * a.p0_stride;
     if (a.p0_sel) in += (long long)a.p0_sel[cw] * a.p0_sel_stride;
     return in;
   } else {
@@ -267,12 +284,13 @@ __device__ __forceinline__ _Float16 prior_of(const void *row, int i) {
 
 // The instances are bp_irregular_lnms_kernel's: P0 priors without Llr, float
 // priors with one LlrIoDev argument, POST also writes the recorded T; CACHED
-// keeps the passes' items in registers (at most kCachePasses passes).
+// keeps the passes' items in registers (at most kCachePasses passes); with an
+// OmsDev argument (the last one) the sweep applies the offset correction.
 // Six waves per SIMD = two workgroups of 12 waves per CU.
-template <int T, bool CACHED, bool POST = false, class... Llr>
+template <int T, bool CACHED, bool POST = false, class... X>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void bp_irregular_lnms_h16_kernel(
-    DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, Llr... io) {
-  constexpr bool LLR = sizeof...(Llr) > 0;
+    DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, X... io) {
+  constexpr bool LLR = pack_has<LlrIoDev, X...>, OMS = pack_has<OmsDev, X...>;
   static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -292,6 +310,11 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
   const LnmsLds s{post, c2v, pass, cols, rowp};
   const _Float16 a16 = (_Float16)a.nms_alpha;
   const h2 alpha = {a16, a16};
+  h2 beta = {(_Float16)0.0f, (_Float16)0.0f};
+  if constexpr (OMS) {
+    const _Float16 b16 = (_Float16)pack_get<OmsDev>(io...).beta;  // RN16
+    beta = h2{b16, b16};
+  }
 
   const int B = a.B_dev ? (int)*a.B_dev : a.B;
   for (;;) {
@@ -356,13 +379,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
 #pragma unroll
         for (int p = 0; p < kCachePasses; ++p)
           if (p < lp.npass) {
-            lnms_pass(s, item[p], alpha);
+            lnms_pass<OMS>(s, item[p], alpha, beta);
             if (last >> p & 1) __syncthreads();  // the layer is complete: the next one reads its posteriors
           }
       } else {
         for (int p = 0; p < lp.npass; ++p) {
           const int w = __builtin_amdgcn_readfirstlane(pass[p]);
-          lnms_pass(s, lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l), alpha);
+          lnms_pass<OMS>(s, lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l), alpha, beta);
           if (w >> 24) __syncthreads();
         }
       }
@@ -390,29 +413,28 @@ int lnms_h16_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev
 }  // namespace
 
 hipError_t launch_bp_irregular_lnms_h16(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp,
-                                        const LlrIoDev *io, hipStream_t s) {
+                                        const LlrIoDev *io, const OmsDev *oms, hipStream_t s) {
   constexpr int T = kIrrThreads;
   static_assert(T / kLanes == kLayRowsPerPass, "the plan's passes are this kernel's");
   size_t lds = 0;
   const int per_cu = lnms_h16_launch_shape(c, a, lp, lds);
   if (!per_cu || (io && !io->llr)) return hipErrorNotSupported;
+  if (oms && !(oms->beta > 0.0f)) oms = nullptr;
   const long long pairs = ((long long)a.B + 1) / 2;  // a workgroup takes two entries at a time
-  const bool cached = lp.npass <= kCachePasses;
-  if (!io) {
-    if (cached)
-      return launch_persistent(bp_irregular_lnms_h16_kernel<T, true>, T, lds, per_cu, pairs, false, a, s, c, a,
-                               a.queue, lp);
-    return launch_persistent(bp_irregular_lnms_h16_kernel<T, false>, T, lds, per_cu, pairs, false, a, s, c, a,
-                             a.queue, lp);
-  }
-  auto go = [&](auto kern) {
-    return launch_persistent(kern, T, lds, per_cu, pairs, false, a, s, c, a, a.queue, lp, *io);
+  auto go = [&](auto kern, const auto &...x) {
+    return launch_persistent(kern, T, lds, per_cu, pairs, false, a, s, c, a, a.queue, lp, x...);
   };
-  if (cached)
-    return io->post ? go(bp_irregular_lnms_h16_kernel<T, true, true, LlrIoDev>)
-                    : go(bp_irregular_lnms_h16_kernel<T, true, false, LlrIoDev>);
-  return io->post ? go(bp_irregular_lnms_h16_kernel<T, false, true, LlrIoDev>)
-                  : go(bp_irregular_lnms_h16_kernel<T, false, false, LlrIoDev>);
+  auto pick = [&](auto cached) {
+    constexpr bool C = decltype(cached)::value;
+    if (!io)
+      return oms ? go(bp_irregular_lnms_h16_kernel<T, C, false, OmsDev>, *oms) : go(bp_irregular_lnms_h16_kernel<T, C>);
+    if (io->post)
+      return oms ? go(bp_irregular_lnms_h16_kernel<T, C, true, LlrIoDev, OmsDev>, *io, *oms)
+                 : go(bp_irregular_lnms_h16_kernel<T, C, true, LlrIoDev>, *io);
+    return oms ? go(bp_irregular_lnms_h16_kernel<T, C, false, LlrIoDev, OmsDev>, *io, *oms)
+               : go(bp_irregular_lnms_h16_kernel<T, C, false, LlrIoDev>, *io);
+  };
+  return lp.npass <= kCachePasses ? pick(std::true_type{}) : pick(std::false_type{});
 }
 
 }  // namespace kml

@@ -41,6 +41,11 @@
 // it as it does in the fp64 kernels); the CN phase closes with wg_any.
 // LDS: irr_slots * 8 + cc_len * 4 (float priors) + 16 + E * 2 (u16 slot table)
 // + N decision bytes: about 85 KB for BG2, one workgroup per CU.
+//
+// The offset instances (kml_set_nms_offset, kernels.hpp OmsDev) put two more
+// operations behind the multiply: c = RN(c - beta), c = c > 0 ? c : +0, ahead of
+// the sign; tests/bp_oms_model.py states them and equals this file's contract at
+// beta = 0.  A context with offset 0 launches the instances without them.
 #include "bp_common.hpp"
 #include "bp_launch.hpp"
 #include "exact_math.hpp"
@@ -107,8 +112,9 @@ __device__ __forceinline__ void nms_vn_any(int d, int2 *slots, const unsigned sh
 // lane holds edges [0, S), the odd lane [S, D), S = (D + 1) / 2; base = the slot
 // of edge 0, the row's edges kIrrCnStride apart.  Returns the row's parity (the
 // XOR of its columns' decisions), the same on both lanes.
-template <int D>
-__device__ __forceinline__ unsigned nms_cn_half(int2 *slots, int base, int odd, float alpha) {
+// OMS: the offset correction (kernels.hpp OmsDev), c = max(RN(c - beta), +0).
+template <int D, bool OMS>
+__device__ __forceinline__ unsigned nms_cn_half(int2 *slots, int base, int odd, float alpha, float beta) {
   constexpr int S = (D + 1) / 2;
   const int first = odd ? S : 0;
   const int own = odd ? D - S : S;
@@ -139,24 +145,26 @@ __device__ __forceinline__ unsigned nms_cn_half(int2 *slots, int base, int odd, 
   for (int j = 0; j < S; ++j) {
     if (j < own) {
       const unsigned a = (m[j] & ~kSignBit) == r1 ? r2 : r1;
-      const float q = alpha * __int_as_float((int)a);
+      float q = alpha * __int_as_float((int)a);
+      if constexpr (OMS) q = fmaxf(q - beta, 0.0f);  // (q - beta is never -0 and never NaN)
       slots[base + (first + j) * kIrrCnStride].x = (int)((unsigned)__float_as_int(q) | ((m[j] ^ rsgn) & kSignBit));
     }
   }
   return rpar;
 }
 
-__device__ __forceinline__ unsigned nms_cn_any(int d, int2 *slots, int base, int odd, float alpha) {
+template <bool OMS>
+__device__ __forceinline__ unsigned nms_cn_any(int d, int2 *slots, int base, int odd, float alpha, float beta) {
   switch (d) {
-    case 2: return nms_cn_half<2>(slots, base, odd, alpha);
-    case 3: return nms_cn_half<3>(slots, base, odd, alpha);
-    case 4: return nms_cn_half<4>(slots, base, odd, alpha);
-    case 5: return nms_cn_half<5>(slots, base, odd, alpha);
-    case 6: return nms_cn_half<6>(slots, base, odd, alpha);
-    case 7: return nms_cn_half<7>(slots, base, odd, alpha);
-    case 8: return nms_cn_half<8>(slots, base, odd, alpha);
-    case 9: return nms_cn_half<9>(slots, base, odd, alpha);
-    default: return nms_cn_half<10>(slots, base, odd, alpha);
+    case 2: return nms_cn_half<2, OMS>(slots, base, odd, alpha, beta);
+    case 3: return nms_cn_half<3, OMS>(slots, base, odd, alpha, beta);
+    case 4: return nms_cn_half<4, OMS>(slots, base, odd, alpha, beta);
+    case 5: return nms_cn_half<5, OMS>(slots, base, odd, alpha, beta);
+    case 6: return nms_cn_half<6, OMS>(slots, base, odd, alpha, beta);
+    case 7: return nms_cn_half<7, OMS>(slots, base, odd, alpha, beta);
+    case 8: return nms_cn_half<8, OMS>(slots, base, odd, alpha, beta);
+    case 9: return nms_cn_half<9, OMS>(slots, base, odd, alpha, beta);
+    default: return nms_cn_half<10, OMS>(slots, base, odd, alpha, beta);
   }
 }
 
@@ -166,17 +174,14 @@ __host__ __device__ inline size_t nms_lds_bytes(const DevCode &c) {
 // ... and with the posterior instance's N floats behind it
 size_t nms_post_lds_bytes(const DevCode &c) { return ((nms_lds_bytes(c) + 3) & ~(size_t)3) + (size_t)c.N * 4; }
 
-// The LLR instances' extra kernel argument (none: the P0 instances).
-__device__ __forceinline__ const LlrIoDev &llr_io(const LlrIoDev &io) { return io; }
-
 // The iterations of one codeword (bp_irregular.hip decode_irr without its
 // FAST / SYN / PROF parts).  Each lane's plan is packed into one word per
 // round (slot base | degree << 14 | column or row << 18; ~0 = no item).
-template <int T, bool POST>
+template <int T, bool POST, bool OMS>
 __device__ __forceinline__ void decode_nms(const DevCode &c, const BpLaunch &a, int2 *slots,
                                            const unsigned short *cslot, const float *pri, unsigned char *cch,
                                            float *tpost, int odd, const int (&vcol)[3], const int (&crow)[3],
-                                           int &iter_out, bool &conv_out) {
+                                           int &iter_out, bool &conv_out, float beta) {
   unsigned vpk[3], cpk[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
@@ -215,7 +220,7 @@ __device__ __forceinline__ void decode_nms(const DevCode &c, const BpLaunch &a, 
 #pragma unroll
     for (int r = 0; r < 3; ++r)
       if (cpk[r] != ~0u)  // both lanes of a pair agree
-        fail |= nms_cn_any(pdeg(cpk[r]), slots, pbase(cpk[r]), odd, alpha);
+        fail |= nms_cn_any<OMS>(pdeg(cpk[r]), slots, pbase(cpk[r]), odd, alpha, beta);
     if (!wg_any<T / 64>(fail != 0, wflags)) {
       conv = true;
       break;
@@ -228,10 +233,11 @@ __device__ __forceinline__ void decode_nms(const DevCode &c, const BpLaunch &a, 
 // The instance without Llr is the P0 front end (the contract above).  With one
 // LlrIoDev argument the priors are the caller's floats, clamped to +-256 (there
 // is no log in that instance), and POST also keeps the T of every VN phase in N
-// more floats of LDS and writes the last one out with the decisions.
-template <int T, bool POST = false, class... Llr>
-__global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch a, unsigned int *queue, Llr... io) {
-  constexpr bool LLR = sizeof...(Llr) > 0;
+// more floats of LDS and writes the last one out with the decisions.  With an
+// OmsDev argument (the last one) the CN phase applies the offset correction.
+template <int T, bool POST = false, class... X>
+__global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch a, unsigned int *queue, X... io) {
+  constexpr bool LLR = pack_has<LlrIoDev, X...>, OMS = pack_has<OmsDev, X...>;
   static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -266,7 +272,7 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
     if (entry >= B) break;
     const int cw = a.cw_idx ? a.cw_idx[entry] : entry;
     if constexpr (LLR) {
-      const float *l = llr_io(io...).llr + (long long)cw * a.p0_stride;
+      const float *l = pack_get<LlrIoDev>(io...).llr + (long long)cw * a.p0_stride;
       if (a.p0_sel) l += (long long)a.p0_sel[cw] * a.p0_sel_stride;
       for (int i = tid; i < c.cc_len; i += T) pri[i] = fminf(fmaxf(l[i], -kNmsClamp), kNmsClamp);
     } else {
@@ -283,7 +289,9 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
 
     int iter = 0;
     bool conv = false;
-    decode_nms<T, POST>(c, a, slots, cslot, pri, cch, tpost, odd, vcol, crow, iter, conv);
+    float beta = 0.0f;
+    if constexpr (OMS) beta = pack_get<OmsDev>(io...).beta;
+    decode_nms<T, POST, OMS>(c, a, slots, cslot, pri, cch, tpost, odd, vcol, crow, iter, conv, beta);
 
     if (a.iter_count > 0) {
       if (a.uu_hat) {
@@ -295,7 +303,7 @@ __global__ __launch_bounds__(T) void bp_irregular_nms_kernel(DevCode c, BpLaunch
         for (int v = tid; v < c.N; v += T) o[v] = cch[v];
       }
       if constexpr (POST) {  // the T of the VN phase these decisions came from
-        float *o = llr_io(io...).post + (long long)cw * c.N;
+        float *o = pack_get<LlrIoDev>(io...).post + (long long)cw * c.N;
         for (int v = tid; v < c.N; v += T) o[v] = tpost[v];
       }
       if (a.parity_cnt) {  // ParityCheck(cc_hat) (:281-300)
@@ -352,30 +360,30 @@ bool bp_irregular_nms_supported(const DevCode &c) {
          nms_lds_bytes(c) <= kLdsLimit;
 }
 
-hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, hipStream_t s) {
-  constexpr int T = kIrrThreads;
-  if (!bp_irregular_nms_supported(c)) return hipErrorNotSupported;
-  if (a.syn || a.cw_prof || a.prof) return hipErrorNotSupported;  // no syndrom_soft, no profile (launch_bp says why)
-  auto kern = bp_irregular_nms_kernel<T>;
-  return launch_persistent(kern, T, nms_lds_bytes(c), 1, kNoGridCap, false, a, s, c, a, a.queue);
-}
-
 bool bp_irregular_nms_post_supported(const DevCode &c) {
   return bp_irregular_nms_supported(c) && nms_post_lds_bytes(c) <= kLdsLimit;
 }
 
-// The LLR front end: float priors (io.llr), and the posterior instance when io.post is set.
-hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const LlrIoDev &io, hipStream_t s) {
+// io = NULL: P0 priors; else float priors (io->llr), and the posterior instance
+// when io->post is set.  oms: the offset instances (beta > 0), else the plain ones.
+hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const LlrIoDev *io, const OmsDev *oms,
+                                   hipStream_t s) {
   constexpr int T = kIrrThreads;
-  if (!bp_irregular_nms_supported(c) || !io.llr) return hipErrorNotSupported;
-  if (a.syn || a.cw_prof || a.prof) return hipErrorNotSupported;
-  if (io.post) {
-    if (!bp_irregular_nms_post_supported(c)) return hipErrorNotSupported;
-    return launch_persistent(bp_irregular_nms_kernel<T, true, LlrIoDev>, T, nms_post_lds_bytes(c), 1, kNoGridCap, false,
-                             a, s, c, a, a.queue, io);
-  }
-  return launch_persistent(bp_irregular_nms_kernel<T, false, LlrIoDev>, T, nms_lds_bytes(c), 1, kNoGridCap, false, a, s,
-                           c, a, a.queue, io);
+  if (!bp_irregular_nms_supported(c) || (io && !io->llr)) return hipErrorNotSupported;
+  if (a.syn || a.cw_prof || a.prof) return hipErrorNotSupported;  // no syndrom_soft, no profile (launch_bp says why)
+  if (oms && !(oms->beta > 0.0f)) oms = nullptr;
+  const bool post = io && io->post;
+  if (post && !bp_irregular_nms_post_supported(c)) return hipErrorNotSupported;
+  const size_t lds = post ? nms_post_lds_bytes(c) : nms_lds_bytes(c);
+  auto go = [&](auto kern, const auto &...x) {
+    return launch_persistent(kern, T, lds, 1, kNoGridCap, false, a, s, c, a, a.queue, x...);
+  };
+  if (!io) return oms ? go(bp_irregular_nms_kernel<T, false, OmsDev>, *oms) : go(bp_irregular_nms_kernel<T>);
+  if (post)
+    return oms ? go(bp_irregular_nms_kernel<T, true, LlrIoDev, OmsDev>, *io, *oms)
+               : go(bp_irregular_nms_kernel<T, true, LlrIoDev>, *io);
+  return oms ? go(bp_irregular_nms_kernel<T, false, LlrIoDev, OmsDev>, *io, *oms)
+             : go(bp_irregular_nms_kernel<T, false, LlrIoDev>, *io);
 }
 
 }  // namespace kml

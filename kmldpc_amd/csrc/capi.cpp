@@ -188,6 +188,7 @@ int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
     c->schedule = KML_SCHED_FLOODING;
     c->demapper = KML_DEMAP_EXACT;  // ... and so does the max-log front end
     c->messages = KML_MSG_F32;      // ... and the binary16 message format
+    c->nms_offset = 0.0f;           // ... and the offset correction
     return KML_OK;
   }
   if (alpha == 0.0) alpha = 0.75;
@@ -298,11 +299,45 @@ int kml_set_messages(kml_ctx *c, int fmt) {
                 "has no binary16 kernel); the context keeps its format");
   if (half_rounds_to_zero(c->nms_alpha))
     return fail(c, KML_E_ARG, "kml_set_messages: the context's alpha rounds to zero in binary16");
+  if (c->nms_offset > 0.0f && half_rounds_to_zero(c->nms_offset))
+    return fail(c, KML_E_ARG, "kml_set_messages: the context's min-sum offset rounds to zero in binary16");
   c->messages = fmt;
   return KML_OK;
 }
 
 int kml_get_messages(const kml_ctx *c) { return c ? c->messages : KML_E_ARG; }
+
+int kml_set_nms_offset(kml_ctx *c, double beta) {
+  if (!c) return KML_E_ARG;
+  call_begin(c);
+  if (!(beta >= 0.0 && beta <= 256.0))  // NaN included
+    return fail(c, KML_E_ARG, "kml_set_nms_offset: beta must be in [0, 256]");
+  if (beta == 0.0) {  // always accepted: the decoders without the correction
+    c->nms_offset = 0.0f;
+    return KML_OK;
+  }
+  const float bf = (float)beta;
+  if (!(bf > 0.0f)) return fail(c, KML_E_ARG, "kml_set_nms_offset: beta rounds to zero in single precision");
+  if (c->messages == KML_MSG_F16 && half_rounds_to_zero(bf))
+    return fail(c, KML_E_ARG,
+                "kml_set_nms_offset: beta rounds to zero in binary16 (KML_MSG_F16); the context keeps its offset");
+  if (c->device < 0 || !c->stream)
+    return fail(c, KML_E_UNSUP, "kml_set_nms_offset: a host-only context (device < 0) has no min-sum decoder");
+  if (kml::bp_generic_forced())
+    return fail(c, KML_E_UNSUP, "kml_set_nms_offset: the offset correction is not available with KML_BP_KERNEL=generic");
+  if (c->algorithm != KML_ALG_NMS)
+    return fail(c, KML_E_UNSUP,
+                "kml_set_nms_offset: the offset correction belongs to the min-sum mode (kml_set_algorithm(KML_ALG_NMS) "
+                "first); the context keeps its offset");
+  c->nms_offset = bf;
+  return KML_OK;
+}
+
+int kml_get_nms_offset(const kml_ctx *c, double *beta) {
+  if (!c || !beta) return KML_E_ARG;
+  *beta = (double)c->nms_offset;
+  return KML_OK;
+}
 
 int kml_dims(const kml_ctx *c, int32_t *d) {
   if (!c || !d) return KML_E_ARG;

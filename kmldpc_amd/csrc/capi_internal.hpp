@@ -76,6 +76,7 @@ struct kml_ctx {
   int schedule = KML_SCHED_FLOODING;  // kml_set_schedule: row schedule of the min-sum decodes
   int demapper = KML_DEMAP_EXACT;   // kml_set_demapper: front end of the min-sum receive path
   int messages = KML_MSG_F32;       // kml_set_messages: message format of the layered min-sum decodes
+  float nms_offset = 0.0f;          // kml_set_nms_offset: the min-sum offset correction (0: none)
   kml::LayeredPlan layered;         // its layers (empty: the code has none, kml_code_layers says KML_E_UNSUP)
   kml::LnmsPlanDev lnms_dev;        // ... and the device copy of the passes (d_lnms)
   hipStream_t stream = nullptr;

@@ -330,10 +330,12 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric, c
   if (llr && (metric || c->algorithm != KML_ALG_NMS))  // (callers check first: no fp64 kernel reads float priors)
     return fail(c, KML_E_UNSUP, "float LLR priors are decoded by the min-sum mode (KML_ALG_NMS) only");
   a.prec = metric ? KML_PREC_F64 : c->precision;
+  kml::OmsDev oms;
   if (!metric && c->algorithm == KML_ALG_NMS) {  // (never with the f32 precision: kml_set_algorithm)
     if (a.syn) return fail(c, KML_E_UNSUP, "the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
     a.prec = c->schedule == KML_SCHED_LAYERED ? (c->messages == KML_MSG_F16 ? 4 : 3) : 2;
     a.nms_alpha = c->nms_alpha;
+    oms.beta = c->nms_offset;  // (> 0 only in this mode: kml_set_nms_offset, kml_set_algorithm)
   }
   int slot = reuse;
   if (reuse < 0) TRY(fresh_slot(c, slot));
@@ -356,7 +358,8 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric, c
   }
   Timer t(c, "bp", slot, (double)a.B * 8.0 * c->code.cc_len);
   const char *msg = nullptr;
-  hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family, &c->lnms_dev, llr);
+  hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family, &c->lnms_dev, llr,
+                                oms.beta > 0.0f ? &oms : nullptr);
   t.stop();
   if (e != hipSuccess) return msg ? fail(c, KML_E_UNSUP, msg) : hip_fail(c, e, "bp launch");
   if (c->inject_abort >= 0 && c->coop_groups > 0 && c->inject_abort-- == 0)  // as if a group barrier timed out

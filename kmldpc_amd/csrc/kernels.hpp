@@ -14,6 +14,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "layout.hpp"  // kIrrThreads, kIrrVnPairMax, kIrrCnPairMax
 
@@ -149,7 +150,7 @@ bool bp_regular_f32_supported(const DevCode &c);
 hipError_t launch_bp_irregular(const DevCode &c, const BpLaunch &a, hipStream_t s);
 // The normalized min-sum sibling (BpLaunch::prec = 2) and whether this code
 // takes it: the codes of launch_bp_irregular whose min-sum state fits in LDS.
-hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, hipStream_t s);
+// (the launcher is declared with its optional arguments, below)
 bool bp_irregular_nms_supported(const DevCode &c);
 // The layered min-sum sibling (BpLaunch::prec = 3, bp_irregular_lnms.hip): the
 // codes of launch_bp_irregular_nms.  Its layer plan (layout.hpp LayeredPlan)
@@ -169,19 +170,39 @@ struct LlrIoDev {
   const float *llr = nullptr;  // priors: L[v] = min(max(llr[v - punct], -256), 256), +0 for a punctured column
   float *post = nullptr;       // [B][N] posteriors the decisions were taken from (optional; iter_count = 0 writes none)
 };
-hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const LlrIoDev &io, hipStream_t s);
+// The offset correction of the three min-sum kernels (kml_set_nms_offset): after
+// c = RN(alpha * a_j) the offset instances run c = RN(c - beta), c = c > 0 ? c
+// : +0 (binary16 in the h16 kernel, with beta rounded once more to binary16).
+// Like LlrIoDev it travels as a kernel argument of its own, behind LlrIoDev
+// where both are present, and only the offset instances take it.  oms = NULL
+// (or beta = 0) launches the instances without it.
+struct OmsDev {
+  float beta = 0.0f;  // > 0
+};
+// The optional arguments of a min-sum kernel are a pack of the types above:
+// which are present picks the instance, and the kernel reads them by type.
+template <class W, class... A>
+constexpr bool pack_has = (std::is_same_v<W, A> || ...);
+template <class W, class A0, class... A>
+__device__ __forceinline__ const W &pack_get(const A0 &a0, const A &...a) {
+  if constexpr (std::is_same_v<W, A0>)
+    return a0;
+  else
+    return pack_get<W>(a...);
+}
+hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const LlrIoDev *io, const OmsDev *oms,
+                                   hipStream_t s);
 // Does the flooding kernel's posterior instance (N more floats of LDS) fit this code?
 bool bp_irregular_nms_post_supported(const DevCode &c);
-hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, hipStream_t s);
-hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev &io,
-                                    hipStream_t s);
+hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev *io,
+                                    const OmsDev *oms, hipStream_t s);
 // The binary16 message format of the layered kernel (BpLaunch::prec = 4,
 // bp_irregular_lnms_h16.hip): the codes, the layer plan and the launch rules of
 // launch_bp_irregular_lnms; two codewords a workgroup, one in each half of a
 // 32-bit word.  io = NULL: P0 priors; else float priors (and posteriors out
 // when io->post is set), as above.
 hipError_t launch_bp_irregular_lnms_h16(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp,
-                                        const LlrIoDev *io, hipStream_t s);
+                                        const LlrIoDev *io, const OmsDev *oms, hipStream_t s);
 // KML_BP_KERNEL=generic (read now, and as the dispatch first read it).
 bool bp_generic_forced();
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of
@@ -206,8 +227,10 @@ int bp_regular_threads(int N, int M, int E, int dv_max, int dc_max, int regular)
 // family (optional) receives the name of the kernel that was launched.
 // lnms: the layer plan, read by prec = 3 only (which fails without one).
 // llr: the LLR front end (prec = 2 and 3 only; any other prec fails with it).
+// oms: the offset correction (the min-sum precs only; any other prec fails with it).
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err,
-                     const char **family = nullptr, const LnmsPlanDev *lnms = nullptr, const LlrIoDev *llr = nullptr);
+                     const char **family = nullptr, const LnmsPlanDev *lnms = nullptr, const LlrIoDev *llr = nullptr,
+                     const OmsDev *oms = nullptr);
 // Workspace the BP launcher needs in global-slot mode (double2 elements).
 long long bp_gslots_needed(const DevCode &c);
 bool bp_uses_lds(const DevCode &c);

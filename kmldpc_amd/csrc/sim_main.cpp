@@ -28,7 +28,10 @@
 // and states itself in the line after the schedule's), KML_MESSAGES (f32 or f16,
 // also `--messages f32|f16`: the message format of the layered min-sum decodes,
 // kml_set_messages; f16 needs nms and layered and states itself in the line
-// after the demapper's).
+// after the demapper's), KML_OFFSET (a number in [0, 256], also `--offset B`:
+// the offset correction of the min-sum check-node rule, kml_set_nms_offset; a
+// B above 0 needs nms and states itself in the line after the message
+// format's; an unparsable or out-of-range B is a usage error, exit status 2).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -110,6 +113,7 @@ int main(int argc, char **argv) {
   std::string sched = getenv("KML_SCHEDULE") ? getenv("KML_SCHEDULE") : "flooding";
   std::string demapper = getenv("KML_DEMAPPER") ? getenv("KML_DEMAPPER") : "exact";
   std::string messages = getenv("KML_MESSAGES") ? getenv("KML_MESSAGES") : "f32";
+  std::string offset = getenv("KML_OFFSET") ? getenv("KML_OFFSET") : "0";
   for (int i = 1; i < argc; i++) {
     const std::string arg = argv[i];
     if (arg == "--precision" && i + 1 < argc)
@@ -132,6 +136,10 @@ int main(int argc, char **argv) {
       messages = argv[++i];
     else if (arg.rfind("--messages=", 0) == 0)
       messages = arg.substr(11);
+    else if (arg == "--offset" && i + 1 < argc)
+      offset = argv[++i];
+    else if (arg.rfind("--offset=", 0) == 0)
+      offset = arg.substr(9);
     else
       cfg = arg;
   }
@@ -177,6 +185,19 @@ int main(int argc, char **argv) {
           "min-sum decoder");
     return 255;
   }
+  double beta = 0.0;
+  {
+    char *end = nullptr;
+    beta = strtod(offset.c_str(), &end);
+    if (offset.empty() || *end != '\0' || !(beta >= 0.0 && beta <= 256.0)) {  // (NaN included)
+      error("--offset / KML_OFFSET must be a number in [0, 256]");
+      return 2;
+    }
+    if (beta > 0.0 && alg != "nms") {
+      error("--offset needs --algorithm nms: the offset correction belongs to the min-sum mode");
+      return 2;
+    }
+  }
   if (prec == "f32") info("BP decode precision: f32 (single precision, not bit-exact with the reference)");
   if (alg == "nms")
     info(fmt("BP decode algorithm: nms (normalized min-sum, alpha = %g; not the reference's decoder)",
@@ -184,6 +205,7 @@ int main(int argc, char **argv) {
   if (sched == "layered") info("BP decode schedule: layered");
   if (demapper == "maxlog") info("Demapper: maxlog (max-log LLR front end; not the reference's demapper)");
   if (messages == "f16") info("BP message format: f16 (binary16 decoder state; two codewords a workgroup)");
+  if (beta != 0.0) info(fmt("BP min-sum offset: %g", (double)(float)beta));
   info("Start simulation");
   {
     FILE *f = fopen(cfg.c_str(), "rb");
@@ -224,6 +246,11 @@ int main(int argc, char **argv) {
     return 255;
   }
   if (messages == "f16" && kml_set_messages(ctx, KML_MSG_F16) != KML_OK) {
+    error(kml_last_error(ctx));
+    kml_destroy(ctx);
+    return 255;
+  }
+  if (beta != 0.0 && kml_set_nms_offset(ctx, beta) != KML_OK) {
     error(kml_last_error(ctx));
     kml_destroy(ctx);
     return 255;

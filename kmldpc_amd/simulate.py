@@ -76,11 +76,12 @@ class Simulator:
     """Simulator (include/simulator.h): constructed from config.toml, Simulate() runs the sweep."""
 
     def __init__(self, config, data_dir=None, device=0, batch=32768, seed=0, dist=None, log=None, comm_backend="nccl",
-                 precision="f64", algorithm="spa", schedule="flooding", demapper="exact", messages="f32"):
+                 precision="f64", algorithm="spa", schedule="flooding", demapper="exact", messages="f32",
+                 offset=0.0):
         self.log = log or Logger(enabled=(dist.get_rank() if dist else 0) == 0)
         self.ctx = Context(config, data_dir=data_dir or os.path.dirname(os.path.abspath(config)), device=device,
                            precision=precision, algorithm=algorithm, schedule=schedule, demapper=demapper,
-                           messages=messages)
+                           messages=messages, offset=offset)
         self.rc = self.ctx.run_config()
         self.batch = int(batch)
         self.seed = int(seed)
@@ -162,6 +163,9 @@ def main(argv=None):
     ap.add_argument("--messages", default=os.environ.get("KML_MESSAGES", "f32"), metavar="f32|f16",
                     help="message format of the layered min-sum decodes: f32 (default) or f16 (opt-in, needs "
                          "--algorithm nms --schedule layered; binary16 state, two codewords a workgroup)")
+    ap.add_argument("--offset", default=os.environ.get("KML_OFFSET", "0"), metavar="B",
+                    help="offset correction of the min-sum check-node rule: 0 (default) or B in (0, 256] (opt-in, "
+                         "needs --algorithm nms; every check-node message becomes max(alpha * a - B, 0))")
     ap.add_argument("--force-dist", action="store_true", default=os.environ.get("KML_FORCE_DIST", "") == "1",
                     help="build the process group (and run its all-reduces) even when WORLD_SIZE is 1, "
                          "e.g. a 1-rank RCCL group under torchrun --nproc-per-node 1")
@@ -193,6 +197,14 @@ def main(argv=None):
     if args.messages == "f16" and not (alg_name == "nms" and args.schedule == "layered"):
         ap.error("--messages f16 needs --algorithm nms --schedule layered: the binary16 format belongs to the "
                  "layered min-sum decoder")
+    try:
+        beta = float(args.offset)
+    except ValueError:
+        beta = -1.0
+    if not 0.0 <= beta <= 256.0:  # (NaN included)
+        ap.error("--offset / KML_OFFSET must be a number in [0, 256]")
+    if beta > 0.0 and alg_name != "nms":
+        ap.error("--offset needs --algorithm nms: the offset correction belongs to the min-sum mode")
     if alg_name == "nms":  # the first line of an nms run states the mode too
         log.info(f"BP decode algorithm: nms (normalized min-sum, alpha = {float(alg_alpha or 0.75):g}; "
                  "not the reference's decoder)")
@@ -202,6 +214,8 @@ def main(argv=None):
         log.info("Demapper: maxlog (max-log LLR front end; not the reference's demapper)")
     if args.messages == "f16":
         log.info("BP message format: f16 (binary16 decoder state; two codewords a workgroup)")
+    if beta != 0.0:
+        log.info(f"BP min-sum offset: {float(np.float32(beta)):g}")
     log.info("Start simulation")
     if not os.path.exists(args.config):
         log.error("Encouter error while opening config.toml")
@@ -220,7 +234,7 @@ def main(argv=None):
         dist = dist_mod
     sim = Simulator(args.config, device=local, batch=args.batch, seed=args.seed, dist=dist, log=log,
                     comm_backend=args.dist_backend, precision=args.precision, algorithm=args.algorithm,
-                    schedule=args.schedule, demapper=args.demapper, messages=args.messages)
+                    schedule=args.schedule, demapper=args.demapper, messages=args.messages, offset=beta)
     sim.Simulate()
     sim.ctx.close()
     if dist is not None:
