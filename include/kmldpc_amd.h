@@ -171,10 +171,24 @@ int kml_get_precision(const kml_ctx *ctx);
  * h_hat are bit-identical in both algorithms.  CNT_REDONE stays 0;
  * kml_prof_read_flops keeps applying the sum-product rule and is not
  * meaningful in this mode.
+ * Layered-only codes.  An irregular code with column degrees in [1, 9] and row
+ * degrees in [2, 10] that does NOT take bp_irregular_kernel (no round plan:
+ * N > 2304, e.g. the BG2 structure at Z > 96) is accepted too when E <= 65535,
+ * M <= 65535, N < 65535 and its posteriors and messages fit one CU's LDS
+ * (4 N + 4 E + N bytes and the pass words within 160 KiB: BG2 at R = 1/2 up to
+ * Z = 384, K = 3840).  Such a code has the layered decoders only (below):
+ * kml_set_algorithm(KML_ALG_NMS) succeeds and leaves the schedule at flooding,
+ * and until kml_set_schedule(KML_SCHED_LAYERED) every decode entry point
+ * (kml_bp_decode, kml_llr_decode, kml_decode_frames, kml_decode_candidates,
+ * kml_sim_decode(_ex), kml_sim_point) returns KML_E_UNSUP before anything is
+ * launched, the demapper and k-means included; kml_last_error names the
+ * schedule setter and the context keeps its state.  Under the exact demapper
+ * such a code's candidate metric decodes are the generic bp_kernel's.
  * KML_E_UNSUP, with the context's algorithm unchanged: a host-only context, a
- * code that does not take bp_irregular_kernel (PEG2304, PEG8064 and the
- * generic-kernel codes), a context in the f32 precision (a guard: no code takes
- * both kernels), and KML_BP_KERNEL=generic.  In NMS mode a non-NULL
+ * code that takes neither bp_irregular_kernel nor the rule above (regular
+ * codes: PEG2304, PEG8064; degrees outside the ranges; codes whose posteriors
+ * and messages exceed one CU), a context in the f32 precision (a guard: no code
+ * takes both kernels), and KML_BP_KERNEL=generic.  In NMS mode a non-NULL
  * syn (min-sum has no syndrom_soft), the soft-syndrome metric (metric_type =
  * 1) and kml_sim_decode_profile return KML_E_UNSUP before anything is
  * launched.  There is no fallback in either direction. */
@@ -218,9 +232,18 @@ int kml_get_algorithm(const kml_ctx *ctx, double *alpha /* may be NULL */);
  * the number of layers nl and writes min(cap, nl + 1) entries of layer_ptr
  * (layer l = rows [layer_ptr[l], layer_ptr[l + 1])); it works on a host-only
  * context and answers KML_E_UNSUP for a code the min-sum mode does not take
- * (5G BG2 K960: 12 layers of 96 rows).
+ * (5G BG2 K960: 12 layers of 96 rows; the layered-only codes of
+ * kml_set_algorithm are taken: BG2's structure at Z = 384 has 12 layers of 384
+ * rows).
+ * Where the code tables (the column of every edge, the row pointers) fit in
+ * LDS beside the decoder state, the kernel stages them there; otherwise, or
+ * with KML_LNMS_TABLES=global in the environment (read once per process), it
+ * runs the global-table instances, which read every lane's share of a pass
+ * from a table in global memory ("bp_irregular_lnms_gt_kernel" /
+ * "bp_irregular_lnms_h16_gt_kernel" in kml_bp_kernel).  Both compute the same.
  * The schedule belongs to the min-sum mode.  KML_SCHED_FLOODING is always
- * accepted.  KML_SCHED_LAYERED returns KML_E_UNSUP, and the context keeps its
+ * accepted (on a layered-only code the decode entry points then answer
+ * KML_E_UNSUP, see kml_set_algorithm).  KML_SCHED_LAYERED returns KML_E_UNSUP, and the context keeps its
  * schedule, on a host-only context, on a context whose algorithm is not
  * KML_ALG_NMS, and with KML_BP_KERNEL=generic; an unknown value returns
  * KML_E_ARG.  kml_set_algorithm(KML_ALG_SPA) returns the schedule to flooding;

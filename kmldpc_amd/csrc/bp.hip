@@ -301,6 +301,16 @@ bool bp_generic_forced() {
   return kernel_variant() == 1 || (k && k[0] == 'g');
 }
 
+// KML_LNMS_TABLES=global forces the layered kernels' global-table instances
+// (tests and A/B measurements on codes whose tables fit in LDS).
+bool lnms_tables_forced_global() {
+  static const bool v = [] {
+    const char *e = getenv("KML_LNMS_TABLES");
+    return e && e[0] == 'g';
+  }();
+  return v;
+}
+
 bool bp_uses_lds(const DevCode &c) { return (long long)c.E * 16 + kRedBytes + c.N <= (long long)kLdsLimit; }
 
 const char *bp_profile_refusal(const DevCode &c, int iter_count) {
@@ -327,7 +337,7 @@ long long bp_gslots_needed(const DevCode &c) {
 }
 
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err, const char **family,
-                     const LnmsPlanDev *lnms, const LlrIoDev *llr, const OmsDev *oms) {
+                     const LnmsPlanDev *lnms, const LlrIoDev *llr, const OmsDev *oms, const LnmsItemsDev *gt) {
   if (a.B <= 0) return hipSuccess;
   if (oms && a.prec != 2 && a.prec != 3 && a.prec != 4) {  // no other family has a min-sum CN rule
     if (err) *err = "the offset correction belongs to the min-sum kernels";
@@ -366,11 +376,13 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
       return hipErrorNotSupported;
     }
     hipError_t e;
+    bool global = false;  // the layered launch took its global-table instance
     // (the offset only picks the instance: the routing on prec is as it was)
     if (h16)
-      e = launch_bp_irregular_lnms_h16(c, a, *lnms, llr, oms, s);
+      e = launch_bp_irregular_lnms_h16(c, a, *lnms, llr, oms, s, gt, &global);
     else
-      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, llr, oms, s) : launch_bp_irregular_nms(c, a, llr, oms, s);
+      e = layered ? launch_bp_irregular_lnms(c, a, *lnms, llr, oms, s, gt, &global)
+                  : launch_bp_irregular_nms(c, a, llr, oms, s);
     if (e == hipErrorNotSupported) {
       if (err)
         *err = h16       ? "the binary16 layered min-sum BP kernel does not take this code or launch"
@@ -378,8 +390,12 @@ hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const c
                          : "the min-sum BP kernel does not take this code or launch";
       return e;
     }
-    if (family)
-      *family = h16 ? "bp_irregular_lnms_h16_kernel" : layered ? "bp_irregular_lnms_kernel" : "bp_irregular_nms_kernel";
+    if (family) {
+      if (global)
+        *family = h16 ? "bp_irregular_lnms_h16_gt_kernel" : "bp_irregular_lnms_gt_kernel";
+      else
+        *family = h16 ? "bp_irregular_lnms_h16_kernel" : layered ? "bp_irregular_lnms_kernel" : "bp_irregular_nms_kernel";
+    }
     return e;
   }
   if (a.prec != 0) {  // the opt-in single-precision mode: its kernel or an error, never another family

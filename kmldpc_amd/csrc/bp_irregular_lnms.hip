@@ -46,6 +46,14 @@
 // column of every edge and the row pointers as u16, N decision bytes: 59.5 KB
 // for BG2, so two workgroups share a CU.
 //
+// The global-table instances (kernels.hpp LnmsItemsDev, the pack's last type)
+// keep the two code tables out of LDS: every lane's share of every pass comes
+// from a table in global memory, one coalesced 8-byte load issued a pass ahead,
+// and LDS holds T, c2v, the pass words, the tallies and the decision bytes only
+// (160,720 B for BG2's structure at Z = 384, one workgroup a CU).  A launch
+// takes them when the tables do not fit, or with KML_LNMS_TABLES=global; they
+// compute the same (DESIGN.md "Layered min-sum beyond one CU's round plan").
+//
 // The offset instances (kml_set_nms_offset, kernels.hpp OmsDev) put two more
 // operations behind the multiply: c = RN(c - beta), c = c > 0 ? c : +0, ahead of
 // the sign; tests/bp_oms_model.py states them and equals this file's contract at
@@ -107,6 +115,26 @@ __device__ __forceinline__ LnmsItem lnms_item(const LnmsLds &s, int first, int n
     }
   }
   return it;
+}
+
+// The global-table instances (kernels.hpp LnmsItemsDev) read the same item,
+// made on the host, with one coalesced 8-byte load, and run `f(p, item)` for
+// every pass p with the next pass's load in flight across f: the load has no
+// address that depends on another load, and by the time a pass needs its item
+// the pass before it has hidden the L2 latency.
+template <int T>
+__device__ __forceinline__ LnmsItem lnms_gt_item(const uint2 *tab, int p, int tid) {
+  const uint2 w = tab[p * T + tid];
+  return LnmsItem{w.x, (int)w.y};
+}
+template <int T, class F>
+__device__ __forceinline__ void lnms_gt_passes(const uint2 *tab, int npass, int tid, F f) {
+  LnmsItem next = lnms_gt_item<T>(tab, 0, tid);
+  for (int p = 0; p < npass; ++p) {
+    const LnmsItem it = next;
+    if (p + 1 < npass) next = lnms_gt_item<T>(tab, p + 1, tid);
+    f(p, it);
+  }
 }
 
 // One pass of a sweep, eight lanes a row.  OMS: the offset correction
@@ -181,6 +209,7 @@ template <int T, bool CACHED, bool POST = false, class... X>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void bp_irregular_lnms_kernel(
     DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, X... io) {
   constexpr bool LLR = pack_has<LlrIoDev, X...>, OMS = pack_has<OmsDev, X...>;
+  constexpr bool GT = pack_has<LnmsItemsDev, X...>;  // the code tables stay in global memory
   static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -192,12 +221,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
   unsigned short *cols = reinterpret_cast<unsigned short *>(red + kRedBytes / 4);
   unsigned short *rowp = cols + c.E;
   unsigned char *cch = reinterpret_cast<unsigned char *>(rowp + c.M + 1);
+  if constexpr (GT) cch = reinterpret_cast<unsigned char *>(cols);  // no tables: the decision bytes follow the tallies
   __shared__ WgVotes wflags;  // wg_any (bp_common.hpp)
 
-  for (int e = tid; e < c.E; e += T) cols[e] = (unsigned short)c.row_col[e];
-  for (int r = tid; r <= c.M; r += T) rowp[r] = (unsigned short)c.row_ptr[r];
+  if constexpr (!GT) {
+    for (int e = tid; e < c.E; e += T) cols[e] = (unsigned short)c.row_col[e];
+    for (int r = tid; r <= c.M; r += T) rowp[r] = (unsigned short)c.row_ptr[r];
+  }
   for (int p = tid; p < lp.npass; p += T) pass[p] = lp.pass[p];
-  const LnmsLds s{post, c2v, pass, cols, rowp};
+  const LnmsLds s{post, c2v, pass, GT ? nullptr : cols, GT ? nullptr : rowp};
+  const uint2 *gtab = nullptr;
+  if constexpr (GT) gtab = pack_get<LnmsItemsDev>(io...).item;
   const float alpha = a.nms_alpha;
   float beta = 0.0f;
   if constexpr (OMS) beta = pack_get<OmsDev>(io...).beta;
@@ -241,7 +275,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
       for (int p = 0; p < kCachePasses; ++p)
         if (p < lp.npass) {
           const int w = __builtin_amdgcn_readfirstlane(pass[p]);
-          item[p] = lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l);
+          if constexpr (GT)
+            item[p] = lnms_gt_item<T>(gtab, p, tid);
+          else
+            item[p] = lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l);
           last |= (unsigned)(w >> 24) << p;
         }
     }
@@ -258,6 +295,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
         for (int p = 0; p < kCachePasses; ++p)
           if (p < lp.npass) odd |= lnms_odd_rows(s, item[p]);
         fail = odd != 0;
+      } else if constexpr (GT) {  // ... and so do the table's
+        unsigned long long odd = 0;
+        lnms_gt_passes<T>(gtab, lp.npass, tid, [&](int, const LnmsItem &it) { odd |= lnms_odd_rows(s, it); });
+        fail = odd != 0;
       } else {
         fail = lnms_parity_fail<T>(s, c.M, g, l);
       }
@@ -273,6 +314,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
             lnms_pass<OMS>(s, item[p], alpha, beta);
             if (last >> p & 1) __syncthreads();  // the layer is complete: the next one reads its posteriors
           }
+      } else if constexpr (GT) {
+        lnms_gt_passes<T>(gtab, lp.npass, tid, [&](int p, const LnmsItem &it) {
+          const int w = __builtin_amdgcn_readfirstlane(pass[p]);
+          lnms_pass<OMS>(s, it, alpha, beta);
+          if (w >> 24) __syncthreads();
+        });
       } else {
         for (int p = 0; p < lp.npass; ++p) {
           const int w = __builtin_amdgcn_readfirstlane(pass[p]);
@@ -341,17 +388,41 @@ size_t lnms_lds_bytes(const DevCode &c, int npass) {
          ((size_t)c.M + 1) * 2 + (size_t)c.N;
 }
 
+// The global-table instances: the same without the two tables.
+size_t lnms_gt_lds_bytes(int N, int E, int npass) {
+  return (size_t)N * 4 + (size_t)E * 4 + (size_t)npass * 4 + kRedBytes + (size_t)N;
+}
+
 }  // namespace
+
+bool lnms_only_shape_ok(int N, int M, int E, int npass) {
+  return npass >= 1 && E <= 65535 && M <= 65535 && N < (int)kNoCol &&
+         lnms_gt_lds_bytes(N, E, npass) + sizeof(WgVotes) <= kLdsLimit;
+}
+
+bool bp_lnms_only_supported(const DevCode &c, int npass) {
+  return !bp_irregular_nms_supported(c) && !c.regular && c.irr_ok && c.dc_max <= 2 * kLanes &&
+         lnms_only_shape_ok(c.N, c.M, c.E, npass);
+}
 
 namespace {
 // What both front ends check, and the launch shape they share: the dynamic LDS
 // and the workgroups per CU (0: the code or the launch is not this kernel's).
-int lnms_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, size_t &lds) {
-  if (!bp_irregular_nms_supported(c)) return 0;
+// global: the global-table instance (the caller has its table), taken when the
+// LDS-table instance does not fit or KML_LNMS_TABLES=global asks for it.
+int lnms_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, bool have_gt, size_t &lds,
+                      bool &global) {
+  if (!lp.pass || lp.npass < 1) return 0;
+  if (!bp_irregular_nms_supported(c) && !bp_lnms_only_supported(c, lp.npass)) return 0;
   if (a.syn || a.cw_prof || a.prof) return 0;  // no syndrom_soft, no profile (launch_bp says why)
-  // row degrees <= 2 * kLanes by bp_irregular_nms_supported; the u16 tables hold E, N and M
-  if (!lp.pass || lp.npass < 1 || c.dc_max > 2 * kLanes || c.E > 65535 || c.N >= (int)kNoCol || c.M > 65535) return 0;
+  // row degrees <= 2 * kLanes by irr_ok; the 16-bit fields hold E, N and M
+  if (c.dc_max > 2 * kLanes || c.E > 65535 || c.N >= (int)kNoCol || c.M > 65535) return 0;
   lds = lnms_lds_bytes(c, lp.npass);
+  global = lnms_tables_forced_global() || lds + sizeof(WgVotes) > kLdsLimit;
+  if (global) {
+    if (!have_gt) return 0;
+    lds = lnms_gt_lds_bytes(c.N, c.E, lp.npass);
+  }
   if (lds + sizeof(WgVotes) > kLdsLimit) return 0;
   // two workgroups per CU where the LDS holds both (no scratch: DESIGN.md)
   return 2 * (lds + sizeof(WgVotes) + 1024) <= kLdsLimit ? 2 : 1;
@@ -361,25 +432,31 @@ int lnms_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp
 // io = NULL: P0 priors; else float priors (io->llr), and the posterior instances
 // when io->post is set.  oms: the offset instances (beta > 0), else the plain ones.
 hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev *io,
-                                    const OmsDev *oms, hipStream_t s) {
+                                    const OmsDev *oms, hipStream_t s, const LnmsItemsDev *gt, bool *global_out) {
   constexpr int T = kIrrThreads;
   static_assert(T / kLanes == kLayRowsPerPass, "the plan's passes are this kernel's");
   size_t lds = 0;
-  const int per_cu = lnms_launch_shape(c, a, lp, lds);
+  bool global = false;
+  const int per_cu = lnms_launch_shape(c, a, lp, gt && gt->item, lds, global);
   if (!per_cu || (io && !io->llr)) return hipErrorNotSupported;
+  if (global_out) *global_out = global;
   if (oms && !(oms->beta > 0.0f)) oms = nullptr;
   auto go = [&](auto kern, const auto &...x) {
     return launch_persistent(kern, T, lds, per_cu, kNoGridCap, false, a, s, c, a, a.queue, lp, x...);
   };
-  auto pick = [&](auto cached) {
+  // g: nothing (the LDS-table instances), or the global-table instances' LnmsItemsDev, the pack's last
+  auto pick = [&](auto cached, const auto &...g) {
     constexpr bool C = decltype(cached)::value;
-    if (!io) return oms ? go(bp_irregular_lnms_kernel<T, C, false, OmsDev>, *oms) : go(bp_irregular_lnms_kernel<T, C>);
+    if (!io)
+      return oms ? go(bp_irregular_lnms_kernel<T, C, false, OmsDev, std::decay_t<decltype(g)>...>, *oms, g...)
+                 : go(bp_irregular_lnms_kernel<T, C, false, std::decay_t<decltype(g)>...>, g...);
     if (io->post)
-      return oms ? go(bp_irregular_lnms_kernel<T, C, true, LlrIoDev, OmsDev>, *io, *oms)
-                 : go(bp_irregular_lnms_kernel<T, C, true, LlrIoDev>, *io);
-    return oms ? go(bp_irregular_lnms_kernel<T, C, false, LlrIoDev, OmsDev>, *io, *oms)
-               : go(bp_irregular_lnms_kernel<T, C, false, LlrIoDev>, *io);
+      return oms ? go(bp_irregular_lnms_kernel<T, C, true, LlrIoDev, OmsDev, std::decay_t<decltype(g)>...>, *io, *oms, g...)
+                 : go(bp_irregular_lnms_kernel<T, C, true, LlrIoDev, std::decay_t<decltype(g)>...>, *io, g...);
+    return oms ? go(bp_irregular_lnms_kernel<T, C, false, LlrIoDev, OmsDev, std::decay_t<decltype(g)>...>, *io, *oms, g...)
+               : go(bp_irregular_lnms_kernel<T, C, false, LlrIoDev, std::decay_t<decltype(g)>...>, *io, g...);
   };
+  if (global) return lp.npass <= kCachePasses ? pick(std::true_type{}, *gt) : pick(std::false_type{}, *gt);
   return lp.npass <= kCachePasses ? pick(std::true_type{}) : pick(std::false_type{});
 }
 

@@ -130,6 +130,24 @@ __device__ __forceinline__ LnmsItem lnms_item(const LnmsLds &s, int first, int n
   return it;
 }
 
+// The global-table instances' item and pass loop, as in bp_irregular_lnms.hip:
+// one coalesced 8-byte load per lane and pass, the next pass's in flight
+// across f(p, item).
+template <int T>
+__device__ __forceinline__ LnmsItem lnms_gt_item(const uint2 *tab, int p, int tid) {
+  const uint2 w = tab[p * T + tid];
+  return LnmsItem{w.x, (int)w.y};
+}
+template <int T, class F>
+__device__ __forceinline__ void lnms_gt_passes(const uint2 *tab, int npass, int tid, F f) {
+  LnmsItem next = lnms_gt_item<T>(tab, 0, tid);
+  for (int p = 0; p < npass; ++p) {
+    const LnmsItem it = next;
+    if (p + 1 < npass) next = lnms_gt_item<T>(tab, p + 1, tid);
+    f(p, it);
+  }
+}
+
 // c2v magnitudes of both halves: RN16(alpha * a), and with OMS the offset
 // correction (kernels.hpp OmsDev) in binary16: a packed subtract, then a packed
 // max with +0 (its operand is never -0: x - x is +0 in round-to-nearest).
@@ -223,7 +241,11 @@ __device__ __forceinline__ void lnms_record(const DevCode &c, const BpLaunch &a,
       int cnt = 0;
       for (int r = tid; r < c.M; r += T) {
         int p = 0;
-        for (int e = s.rowp[r]; e < s.rowp[r + 1]; ++e) p ^= cch[s.cols[e]];
+        if constexpr (pack_has<LnmsItemsDev, X...>) {  // no tables in LDS: the graph as uploaded
+          for (int e = c.row_ptr[r]; e < c.row_ptr[r + 1]; ++e) p ^= cch[c.row_col[e]];
+        } else {
+          for (int e = s.rowp[r]; e < s.rowp[r + 1]; ++e) p ^= cch[s.cols[e]];
+        }
         cnt += p;
       }
       if (cnt) atomicAdd(&red[0], cnt);
@@ -291,6 +313,7 @@ template <int T, bool CACHED, bool POST = false, class... X>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void bp_irregular_lnms_h16_kernel(
     DevCode c, BpLaunch a, unsigned int *queue, LnmsPlanDev lp, X... io) {
   constexpr bool LLR = pack_has<LlrIoDev, X...>, OMS = pack_has<OmsDev, X...>;
+  constexpr bool GT = pack_has<LnmsItemsDev, X...>;  // the code tables stay in global memory
   static_assert(LLR || !POST, "the posterior output belongs to the LLR instances");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -302,12 +325,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
   unsigned short *cols = reinterpret_cast<unsigned short *>(red + kRedBytes / 4);
   unsigned short *rowp = cols + c.E;
   unsigned char *cch = reinterpret_cast<unsigned char *>(rowp + c.M + 1);
+  if constexpr (GT) cch = reinterpret_cast<unsigned char *>(cols);  // no tables: the decision bytes follow the tallies
   __shared__ WgVotes wflags;  // wg_any2 (bp_common.hpp)
 
-  for (int e = tid; e < c.E; e += T) cols[e] = (unsigned short)c.row_col[e];
-  for (int r = tid; r <= c.M; r += T) rowp[r] = (unsigned short)c.row_ptr[r];
+  if constexpr (!GT) {
+    for (int e = tid; e < c.E; e += T) cols[e] = (unsigned short)c.row_col[e];
+    for (int r = tid; r <= c.M; r += T) rowp[r] = (unsigned short)c.row_ptr[r];
+  }
   for (int p = tid; p < lp.npass; p += T) pass[p] = lp.pass[p];
-  const LnmsLds s{post, c2v, pass, cols, rowp};
+  const LnmsLds s{post, c2v, pass, GT ? nullptr : cols, GT ? nullptr : rowp};
+  const uint2 *gtab = nullptr;
+  if constexpr (GT) gtab = pack_get<LnmsItemsDev>(io...).item;
   const _Float16 a16 = (_Float16)a.nms_alpha;
   const h2 alpha = {a16, a16};
   h2 beta = {(_Float16)0.0f, (_Float16)0.0f};
@@ -350,7 +378,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
       for (int p = 0; p < kCachePasses; ++p)
         if (p < lp.npass) {
           const int w = __builtin_amdgcn_readfirstlane(pass[p]);
-          item[p] = lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l);
+          if constexpr (GT)
+            item[p] = lnms_gt_item<T>(gtab, p, tid);
+          else
+            item[p] = lnms_item(s, w & 0xFFFF, (w >> 16) & 0xFF, g, l);
           last |= (unsigned)(w >> 24) << p;
         }
     }
@@ -365,6 +396,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
 #pragma unroll
         for (int p = 0; p < kCachePasses; ++p)
           if (p < lp.npass) odd |= lnms_odd_rows(s, item[p]);
+      } else if constexpr (GT) {  // ... and so do the table's
+        lnms_gt_passes<T>(gtab, lp.npass, tid, [&](int, const LnmsItem &it) { odd |= lnms_odd_rows(s, it); });
       } else {
         for (int first = 0; first < c.M; first += T / kLanes)
           odd |= lnms_odd_rows(s, lnms_item(s, first, c.M - first, g, l));
@@ -382,6 +415,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void 
             lnms_pass<OMS>(s, item[p], alpha, beta);
             if (last >> p & 1) __syncthreads();  // the layer is complete: the next one reads its posteriors
           }
+      } else if constexpr (GT) {
+        lnms_gt_passes<T>(gtab, lp.npass, tid, [&](int p, const LnmsItem &it) {
+          const int w = __builtin_amdgcn_readfirstlane(pass[p]);
+          lnms_pass<OMS>(s, it, alpha, beta);
+          if (w >> 24) __syncthreads();
+        });
       } else {
         for (int p = 0; p < lp.npass; ++p) {
           const int w = __builtin_amdgcn_readfirstlane(pass[p]);
@@ -401,11 +440,20 @@ size_t lnms_h16_lds_bytes(const DevCode &c, int npass) {
 
 // The code and launch rules of bp_irregular_lnms.hip's lnms_launch_shape, on
 // this kernel's LDS (the same bytes): 0 = not this kernel's, else workgroups per CU.
-int lnms_h16_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, size_t &lds) {
-  if (!bp_irregular_nms_supported(c)) return 0;
+// global: the global-table instance, as in bp_irregular_lnms.hip (its LDS is
+// the decoder state: no tables).
+int lnms_h16_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, bool have_gt, size_t &lds,
+                          bool &global) {
+  if (!lp.pass || lp.npass < 1) return 0;
+  if (!bp_irregular_nms_supported(c) && !bp_lnms_only_supported(c, lp.npass)) return 0;
   if (a.syn || a.cw_prof || a.prof) return 0;
-  if (!lp.pass || lp.npass < 1 || c.dc_max > 2 * kLanes || c.E > 65535 || c.N >= (int)kNoCol || c.M > 65535) return 0;
+  if (c.dc_max > 2 * kLanes || c.E > 65535 || c.N >= (int)kNoCol || c.M > 65535) return 0;
   lds = lnms_h16_lds_bytes(c, lp.npass);
+  global = lnms_tables_forced_global() || lds + sizeof(WgVotes) > kLdsLimit;
+  if (global) {
+    if (!have_gt) return 0;
+    lds = (size_t)c.N * 4 + (size_t)c.E * 4 + (size_t)lp.npass * 4 + kRedBytes + (size_t)c.N;
+  }
   if (lds + sizeof(WgVotes) > kLdsLimit) return 0;
   return 2 * (lds + sizeof(WgVotes) + 1024) <= kLdsLimit ? 2 : 1;
 }
@@ -413,27 +461,35 @@ int lnms_h16_launch_shape(const DevCode &c, const BpLaunch &a, const LnmsPlanDev
 }  // namespace
 
 hipError_t launch_bp_irregular_lnms_h16(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp,
-                                        const LlrIoDev *io, const OmsDev *oms, hipStream_t s) {
+                                        const LlrIoDev *io, const OmsDev *oms, hipStream_t s,
+                                        const LnmsItemsDev *gt, bool *global_out) {
   constexpr int T = kIrrThreads;
   static_assert(T / kLanes == kLayRowsPerPass, "the plan's passes are this kernel's");
   size_t lds = 0;
-  const int per_cu = lnms_h16_launch_shape(c, a, lp, lds);
+  bool global = false;
+  const int per_cu = lnms_h16_launch_shape(c, a, lp, gt && gt->item, lds, global);
   if (!per_cu || (io && !io->llr)) return hipErrorNotSupported;
+  if (global_out) *global_out = global;
   if (oms && !(oms->beta > 0.0f)) oms = nullptr;
   const long long pairs = ((long long)a.B + 1) / 2;  // a workgroup takes two entries at a time
   auto go = [&](auto kern, const auto &...x) {
     return launch_persistent(kern, T, lds, per_cu, pairs, false, a, s, c, a, a.queue, lp, x...);
   };
-  auto pick = [&](auto cached) {
+  // g: nothing (the LDS-table instances), or the global-table instances' LnmsItemsDev, the pack's last
+  auto pick = [&](auto cached, const auto &...g) {
     constexpr bool C = decltype(cached)::value;
     if (!io)
-      return oms ? go(bp_irregular_lnms_h16_kernel<T, C, false, OmsDev>, *oms) : go(bp_irregular_lnms_h16_kernel<T, C>);
+      return oms ? go(bp_irregular_lnms_h16_kernel<T, C, false, OmsDev, std::decay_t<decltype(g)>...>, *oms, g...)
+                 : go(bp_irregular_lnms_h16_kernel<T, C, false, std::decay_t<decltype(g)>...>, g...);
     if (io->post)
-      return oms ? go(bp_irregular_lnms_h16_kernel<T, C, true, LlrIoDev, OmsDev>, *io, *oms)
-                 : go(bp_irregular_lnms_h16_kernel<T, C, true, LlrIoDev>, *io);
-    return oms ? go(bp_irregular_lnms_h16_kernel<T, C, false, LlrIoDev, OmsDev>, *io, *oms)
-               : go(bp_irregular_lnms_h16_kernel<T, C, false, LlrIoDev>, *io);
+      return oms ? go(bp_irregular_lnms_h16_kernel<T, C, true, LlrIoDev, OmsDev, std::decay_t<decltype(g)>...>, *io, *oms,
+                      g...)
+                 : go(bp_irregular_lnms_h16_kernel<T, C, true, LlrIoDev, std::decay_t<decltype(g)>...>, *io, g...);
+    return oms ? go(bp_irregular_lnms_h16_kernel<T, C, false, LlrIoDev, OmsDev, std::decay_t<decltype(g)>...>, *io, *oms,
+                    g...)
+               : go(bp_irregular_lnms_h16_kernel<T, C, false, LlrIoDev, std::decay_t<decltype(g)>...>, *io, g...);
   };
+  if (global) return lp.npass <= kCachePasses ? pick(std::true_type{}, *gt) : pick(std::false_type{}, *gt);
   return lp.npass <= kCachePasses ? pick(std::true_type{}) : pick(std::false_type{});
 }
 

@@ -206,10 +206,12 @@ int kml_set_algorithm(kml_ctx *c, int alg, double alpha) {
     return fail(c, KML_E_UNSUP, "kml_set_algorithm: the min-sum decoder is not available in the f32 precision");
   if (kml::bp_generic_forced())
     return fail(c, KML_E_UNSUP, "kml_set_algorithm: the min-sum decoder is not available with KML_BP_KERNEL=generic");
-  if (!kml::bp_irregular_nms_supported(c->dc))
+  if (!kml::bp_irregular_nms_supported(c->dc) && !c->lnms_only)
     return fail(c, KML_E_UNSUP,
                 "kml_set_algorithm: the min-sum decoder takes only the codes of bp_irregular_kernel (column degrees "
-                "<= 9, row degrees in [2, 10], messages in LDS); the context keeps its algorithm");
+                "<= 9, row degrees in [2, 10], messages in LDS) and, in the layered schedule only, irregular codes of "
+                "those degrees with E, M <= 65535, N < 65535 whose posteriors and messages (4 N + 4 E bytes) fit one "
+                "CU's LDS; the context keeps its algorithm");
   c->algorithm = alg;
   c->nms_alpha = af;
   return KML_OK;
@@ -394,6 +396,7 @@ int kml_bp_decode(kml_ctx *c, const double *p0, int B, int iter_count, uint8_t *
   const bool ok = c && p0 && B >= 0 && iter_count >= 0;
   if (ok && B == 0) return KML_OK;
   TRY(gpu_begin(c, ok, "kml_bp_decode: bad argument"));
+  TRY(schedule_refusal(c, "kml_bp_decode"));
   if (syn && c->algorithm == KML_ALG_NMS)
     return fail(c, KML_E_UNSUP, "kml_bp_decode: the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
   const kml::LdpcCode &L = c->code;
@@ -476,6 +479,7 @@ int kml_llr_decode(kml_ctx *c, const float *llr, int B, int iter_count, uint8_t 
       return fail(c, KML_E_UNSUP,
                   "kml_llr_decode: float LLRs are decoded by the min-sum mode only (kml_set_algorithm(KML_ALG_NMS) "
                   "first)");
+    TRY(schedule_refusal(c, "kml_llr_decode"));
     if (llr_out && c->schedule == KML_SCHED_FLOODING && !kml::bp_irregular_nms_post_supported(c->dc))
       return fail(c, KML_E_UNSUP,
                   "kml_llr_decode: the flooding kernel's posterior output (N more floats of LDS) does not fit this code; "
@@ -591,6 +595,7 @@ int kml_decode_frames(kml_ctx *c, const double *y, const double *true_h, double 
   const bool ok = c && y && uu_hat && B >= 0;
   if (ok && B == 0) return KML_OK;
   TRY(gpu_begin(c, ok, "kml_decode_frames: bad argument"));
+  TRY(schedule_refusal(c, "kml_decode_frames"));
   if (!(flags & (KML_DEVICE_PTRS | KML_HISTOGRAM)) && (true_h || !c->rc.metric_soft)) {
     const int CH = host_chunk();
     if (CH > 0 && B > CH) {
@@ -638,6 +643,7 @@ int kml_decode_candidates(kml_ctx *c, const double *y, const double *h_hats, int
   if (ok && nc == 1) return kml_decode_frames(c, y, h_hats, snr, B, uu_hat, chosen, metrics, ret, nullptr, flags);
   if (ok && B == 0) return KML_OK;
   TRY(gpu_begin(c, ok, "kml_decode_candidates: bad argument (need 1 <= nc <= 4)"));
+  TRY(schedule_refusal(c, "kml_decode_candidates"));
   const int S = c->code.cc_len / c->modem.bits;
   const double *d_y, *d_hc;
   TRY(stage_in(c, c->w_y, y, (size_t)B * S * 2, flags, d_y));
@@ -699,6 +705,7 @@ int kml_sim_generate(kml_ctx *c, double snr, uint64_t seed, uint64_t first_cw, i
 
 int kml_sim_decode(kml_ctx *c, double snr, int blind, uint64_t *counters, int do_sync) {
   TRY(gpu_begin(c, do_sync || !counters, "counters need sync != 0"));
+  TRY(schedule_refusal(c, "kml_sim_decode"));
   if (c->sim_B == 0) return KML_OK;
   int slot = 0;
   TRY(sim_receive(c, snr, blind, false, slot));
@@ -708,6 +715,7 @@ int kml_sim_decode(kml_ctx *c, double snr, int blind, uint64_t *counters, int do
 int kml_sim_decode_ex(kml_ctx *c, double snr, int blind, int histogram, int32_t *cw_err, double *metrics,
                       uint64_t *counters) {
   TRY(gpu_begin(c));
+  TRY(schedule_refusal(c, "kml_sim_decode_ex"));
   const size_t B = (size_t)c->sim_B;
   if (B == 0) {
     if (counters) memset(counters, 0, sizeof(uint64_t) * kml::CNT_N);

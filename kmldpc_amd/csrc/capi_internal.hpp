@@ -79,6 +79,8 @@ struct kml_ctx {
   float nms_offset = 0.0f;          // kml_set_nms_offset: the min-sum offset correction (0: none)
   kml::LayeredPlan layered;         // its layers (empty: the code has none, kml_code_layers says KML_E_UNSUP)
   kml::LnmsPlanDev lnms_dev;        // ... and the device copy of the passes (d_lnms)
+  kml::LnmsItemsDev lnms_items;     // ... and of the global-table instances' items (d_lnms_items)
+  bool lnms_only = false;           // the code's only min-sum decoders are the layered ones (kernels.hpp bp_lnms_only_supported)
   hipStream_t stream = nullptr;
   hipStream_t cstream = nullptr;  // host-buffer frame uploads (kml_decode_frames' chunked path), made on first use
   kml::RunConfig rc;
@@ -88,7 +90,7 @@ struct kml_ctx {
   double rot[8];
   using DBuf = kml_host::DBuf;
   // resident constants
-  DBuf d_graph, d_cons, d_lnms;
+  DBuf d_graph, d_cons, d_lnms, d_lnms_items;
   // algorithmic fp64 flops per executed VN / CN phase ("Roofline")
   double vn_flops = 0, cn_flops = 0;
   DBuf d_arena;  // kArenaSlots x CNT_N counters
@@ -141,6 +143,11 @@ inline void call_begin(kml_ctx *c) {
 // own argument check (its result and its message; no message = a bare
 // KML_E_ARG), a context that has a GPU, and that GPU current.
 int gpu_begin(kml_ctx *c, bool args_ok = true, const char *bad_args = nullptr);
+// The schedule rule of a layered-only code (kml_ctx::lnms_only): in the
+// min-sum mode under the flooding schedule there is no kernel to decode with,
+// so every decode entry point asks here before it stages or launches anything.
+// KML_OK, or KML_E_UNSUP with the message set; the context keeps its state.
+int schedule_refusal(kml_ctx *c, const char *who);
 int finish_create(kml_ctx *c);
 void destroy(kml_ctx *c);
 void drain_profile(kml_ctx *c);

@@ -50,6 +50,14 @@ int gpu_begin(kml_ctx *c, bool args_ok, const char *bad_args) {
   return KML_OK;
 }
 
+int schedule_refusal(kml_ctx *c, const char *who) {
+  if (!c->lnms_only || c->algorithm != KML_ALG_NMS || c->schedule != KML_SCHED_FLOODING) return KML_OK;
+  return fail(c, KML_E_UNSUP,
+              std::string(who) +
+                  ": this code's min-sum decoders are the layered ones only (it has no round plan of the flooding "
+                  "kernel): kml_set_schedule(KML_SCHED_LAYERED) first; nothing was launched");
+}
+
 namespace {
 // Packs the graph's arrays into one device allocation: add() each array,
 // copy `host` to the device once, then ptr() each handle.
@@ -193,20 +201,35 @@ int upload_code(kml_ctx *c) {
   }
   // layer plan of the layered min-sum kernel (layout.hpp LayeredPlan), in an
   // allocation of its own: it reaches the kernel beside DevCode, not in it
-  if (kml::bp_irregular_nms_supported(d)) {
+  bool planned = kml::bp_irregular_nms_supported(d);
+  if (planned) {
     kml::plan_layered(L, c->layered);
+  } else if (!regular && irr_ok) {  // a layered-only code?  (the gate needs the plan's pass count)
+    kml::plan_layered(L, c->layered);
+    planned = c->lnms_only = kml::bp_lnms_only_supported(d, (int)c->layered.pass.size());
+    if (!planned) c->layered = kml::LayeredPlan();
+  }
+  if (planned) {
     const size_t bytes = c->layered.pass.size() * sizeof(int32_t);
     HIPCHK(c, c->d_lnms.ensure(bytes), "hipMalloc(layer plan)");
     HIPCHK(c, hipMemcpy(c->d_lnms.p, c->layered.pass.data(), bytes, hipMemcpyHostToDevice), "upload layer plan");
     c->lnms_dev.pass = c->d_lnms.as<int32_t>();
     c->lnms_dev.npass = (int)c->layered.pass.size();
+    // ... and every lane's share of every pass, for the global-table instances
+    std::vector<uint32_t> items;
+    if (kml::layered_items(L, c->layered, items)) {
+      HIPCHK(c, c->d_lnms_items.ensure(items.size() * sizeof(uint32_t)), "hipMalloc(layer items)");
+      HIPCHK(c, hipMemcpy(c->d_lnms_items.p, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice),
+             "upload layer items");
+      c->lnms_items.item = c->d_lnms_items.as<uint2>();
+    }
   }
   return KML_OK;
 }
 
-// The layer plan of a host-only context: bp_irregular_nms_supported restated
-// on the host plan (no DevCode without a GPU), so kml_code_layers answers for
-// the same codes with and without one.
+// The layer plan of a host-only context: bp_irregular_nms_supported and
+// bp_lnms_only_supported restated on the host plan (no DevCode without a GPU),
+// so kml_code_layers answers for the same codes with and without one.
 void plan_layers_host(kml_ctx *c) {
   const kml::LdpcCode &L = c->code;
   bool regular = true, irr_ok = true;
@@ -220,14 +243,20 @@ void plan_layers_host(kml_ctx *c) {
     regular &= dc == L.dc_max;
     irr_ok &= dc >= 2 && dc <= 10;
   }
-  kml::IrregularPlan irr;
-  if (regular || !irr_ok || !kml::plan_irregular(L, kml::kIrrThreads, kml::kIrrVnPairMax, kml::kIrrCnPairMax, irr))
-    return;
-  const size_t fixed = (size_t)L.E * 2 + 16 + (size_t)L.N;  // the slot table, the tallies, the decision bytes
-  const size_t sibling = (size_t)irr.n_slots * 16 + (size_t)L.cc_len * 8 + fixed;
-  const size_t nms = (size_t)irr.n_slots * 8 + (size_t)L.cc_len * 4 + fixed;
-  if (irr.n_slots > 16383 || sibling > kml::kLdsLimit || nms > kml::kLdsLimit) return;
+  if (regular || !irr_ok) return;
   kml::plan_layered(L, c->layered);
+  kml::IrregularPlan irr;
+  bool nms_ok = kml::plan_irregular(L, kml::kIrrThreads, kml::kIrrVnPairMax, kml::kIrrCnPairMax, irr);
+  if (nms_ok) {
+    const size_t fixed = (size_t)L.E * 2 + 16 + (size_t)L.N;  // the slot table, the tallies, the decision bytes
+    const size_t sibling = (size_t)irr.n_slots * 16 + (size_t)L.cc_len * 8 + fixed;
+    const size_t nms = (size_t)irr.n_slots * 8 + (size_t)L.cc_len * 4 + fixed;
+    nms_ok = irr.n_slots <= 16383 && sibling <= kml::kLdsLimit && nms <= kml::kLdsLimit;
+  }
+  if (nms_ok) return;
+  // ... and bp_lnms_only_supported: the layered-only codes
+  c->lnms_only = kml::lnms_only_shape_ok(L.N, L.M, L.E, (int)c->layered.pass.size());
+  if (!c->lnms_only) c->layered = kml::LayeredPlan();
 }
 
 // FP64 work of one VN / CN phase of the exact algorithm: per column of degree
@@ -330,6 +359,7 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric, c
   if (llr && (metric || c->algorithm != KML_ALG_NMS))  // (callers check first: no fp64 kernel reads float priors)
     return fail(c, KML_E_UNSUP, "float LLR priors are decoded by the min-sum mode (KML_ALG_NMS) only");
   a.prec = metric ? KML_PREC_F64 : c->precision;
+  if (!metric) TRY(schedule_refusal(c, "bp launch"));  // (the entry points ask first)
   kml::OmsDev oms;
   if (!metric && c->algorithm == KML_ALG_NMS) {  // (never with the f32 precision: kml_set_algorithm)
     if (a.syn) return fail(c, KML_E_UNSUP, "the min-sum decoder (KML_ALG_NMS) has no syndrom_soft: syn must be NULL");
@@ -359,7 +389,7 @@ int run_bp(kml_ctx *c, kml::BpLaunch a, int *slot_out, int reuse, bool metric, c
   Timer t(c, "bp", slot, (double)a.B * 8.0 * c->code.cc_len);
   const char *msg = nullptr;
   hipError_t e = kml::launch_bp(c->dc, a, c->stream, &msg, &c->bp_family, &c->lnms_dev, llr,
-                                oms.beta > 0.0f ? &oms : nullptr);
+                                oms.beta > 0.0f ? &oms : nullptr, &c->lnms_items);
   t.stop();
   if (e != hipSuccess) return msg ? fail(c, KML_E_UNSUP, msg) : hip_fail(c, e, "bp launch");
   if (c->inject_abort >= 0 && c->coop_groups > 0 && c->inject_abort-- == 0)  // as if a group barrier timed out

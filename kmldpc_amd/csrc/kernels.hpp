@@ -179,6 +179,17 @@ struct LlrIoDev {
 struct OmsDev {
   float beta = 0.0f;  // > 0
 };
+// The global-table instances of the two layered kernels (DESIGN.md "Layered
+// min-sum beyond one CU's round plan"): the code tables stay in global memory
+// and LDS holds the decoder state only.  The table is every lane's share of
+// every pass, made once on the host (layout.hpp layered_items): entry
+// p * kIrrThreads + tid = (v0 | v1 << 16, e0) of thread tid in pass p, so a pass
+// costs a lane one coalesced 8-byte load with no address that depends on
+// another load.  Like LlrIoDev it travels as a kernel argument of its own, the
+// last one, and only the global-table instances take it.
+struct LnmsItemsDev {
+  const uint2 *item = nullptr;  // [npass * kIrrThreads]
+};
 // The optional arguments of a min-sum kernel are a pack of the types above:
 // which are present picks the instance, and the kernel reads them by type.
 template <class W, class... A>
@@ -194,15 +205,33 @@ hipError_t launch_bp_irregular_nms(const DevCode &c, const BpLaunch &a, const Ll
                                    hipStream_t s);
 // Does the flooding kernel's posterior instance (N more floats of LDS) fit this code?
 bool bp_irregular_nms_post_supported(const DevCode &c);
+// gt: the global-table instances' table, or NULL (then only the LDS-table
+// instances can run).  A launch takes the LDS-table instance when its LDS fits
+// and KML_LNMS_TABLES=global is not set, the global-table instance otherwise;
+// global_out (optional) says which it was.
 hipError_t launch_bp_irregular_lnms(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp, const LlrIoDev *io,
-                                    const OmsDev *oms, hipStream_t s);
+                                    const OmsDev *oms, hipStream_t s, const LnmsItemsDev *gt = nullptr,
+                                    bool *global_out = nullptr);
+// The "layered-only" codes: not bp_irregular_nms_supported (no round plan of
+// bp_irregular_kernel, or its LDS does not fit), yet irregular with irr_ok,
+// E, M <= 65535, N < 65535 (the 16-bit fields of the pass words and the
+// items), and the global-table instance's LDS (the decoder state of a code
+// with npass passes) within one CU.  Both layered kernels take them; the
+// flooding kernel does not.
+bool bp_lnms_only_supported(const DevCode &c, int npass);
+// The same rule on plain numbers, for the host plan of a context without a GPU.
+bool lnms_only_shape_ok(int N, int M, int E, int npass);
+// KML_LNMS_TABLES=global (read once per process): every layered launch takes
+// the global-table instance.
+bool lnms_tables_forced_global();
 // The binary16 message format of the layered kernel (BpLaunch::prec = 4,
 // bp_irregular_lnms_h16.hip): the codes, the layer plan and the launch rules of
 // launch_bp_irregular_lnms; two codewords a workgroup, one in each half of a
 // 32-bit word.  io = NULL: P0 priors; else float priors (and posteriors out
 // when io->post is set), as above.
 hipError_t launch_bp_irregular_lnms_h16(const DevCode &c, const BpLaunch &a, const LnmsPlanDev &lp,
-                                        const LlrIoDev *io, const OmsDev *oms, hipStream_t s);
+                                        const LlrIoDev *io, const OmsDev *oms, hipStream_t s,
+                                        const LnmsItemsDev *gt = nullptr, bool *global_out = nullptr);
 // KML_BP_KERNEL=generic (read now, and as the dispatch first read it).
 bool bp_generic_forced();
 // Cooperative kernel for regular codes whose slots exceed the LDS: groups of
@@ -228,9 +257,11 @@ int bp_regular_threads(int N, int M, int E, int dv_max, int dc_max, int regular)
 // lnms: the layer plan, read by prec = 3 only (which fails without one).
 // llr: the LLR front end (prec = 2 and 3 only; any other prec fails with it).
 // oms: the offset correction (the min-sum precs only; any other prec fails with it).
+// gt: the layered kernels' global-table instances (prec = 3 and 4 read it; their
+// family is then "bp_irregular_lnms_gt_kernel" / "bp_irregular_lnms_h16_gt_kernel").
 hipError_t launch_bp(const DevCode &c, const BpLaunch &a, hipStream_t s, const char **err,
                      const char **family = nullptr, const LnmsPlanDev *lnms = nullptr, const LlrIoDev *llr = nullptr,
-                     const OmsDev *oms = nullptr);
+                     const OmsDev *oms = nullptr, const LnmsItemsDev *gt = nullptr);
 // Workspace the BP launcher needs in global-slot mode (double2 elements).
 long long bp_gslots_needed(const DevCode &c);
 bool bp_uses_lds(const DevCode &c);

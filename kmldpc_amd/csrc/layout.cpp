@@ -833,4 +833,25 @@ void plan_layered(const LdpcCode &L, LayeredPlan &out) {
   out.layer_ptr.push_back(L.M);
 }
 
+bool layered_items(const LdpcCode &L, const LayeredPlan &plan, std::vector<uint32_t> &out) {
+  out.clear();
+  if (L.E > 65535 || L.N >= 65535 || L.M > 65535) return false;  // (the pass words hold 16 bits of the first row)
+  out.assign(plan.pass.size() * (size_t)kIrrThreads * 2, 0);
+  for (size_t p = 0; p < plan.pass.size(); ++p) {
+    const int first = plan.pass[p] & 0xFFFF, nrows = (plan.pass[p] >> 16) & 0xFF;
+    for (int t = 0; t < kIrrThreads; ++t) {
+      uint32_t *w = &out[(p * kIrrThreads + t) * 2];
+      const int g = t / kLayLanesPerRow, l = t % kLayLanesPerRow;
+      w[0] = ~0u;
+      if (g >= nrows) continue;
+      const int b = L.row_ptr[first + g], d = L.row_ptr[first + g + 1] - b;
+      if (d > 2 * kLayLanesPerRow) return false;
+      if (l >= d) continue;
+      w[0] = (uint32_t)L.row_col[b + l] | (l + kLayLanesPerRow < d ? (uint32_t)L.row_col[b + l + kLayLanesPerRow] : 0xFFFFu) << 16;
+      w[1] = (uint32_t)(b + l);
+    }
+  }
+  return true;
+}
+
 }  // namespace kml

@@ -154,5 +154,14 @@ struct LayeredPlan {
 // Any code (rows of any degree); the kernel's own limits are the launcher's.
 void plan_layered(const LdpcCode &L, LayeredPlan &out);
 
+// Every lane's share of every pass of a plan, for the layered kernels'
+// global-table instances (kernels.hpp LnmsItemsDev): two words per entry,
+// entry p * kIrrThreads + t = thread t in pass p.  Lane l = t % 8 of row
+// g = t / 8 of the pass takes the row's edges l and l + 8: word 0 = their
+// columns v0 | v1 << 16 (0xFFFF: no such edge), word 1 = the index of edge l.
+// An idle lane holds (0xFFFFFFFF, 0).  Needs E <= 65535 and N < 65535, and row
+// degrees <= 16 (false otherwise: the codes the kernels refuse).
+bool layered_items(const LdpcCode &L, const LayeredPlan &plan, std::vector<uint32_t> &out);
+
 }  // namespace kml
 

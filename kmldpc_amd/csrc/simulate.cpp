@@ -111,9 +111,16 @@ int gpu_batch(uint64_t first, int count, int32_t *cw_err, double *metrics, void 
 }
 }  // namespace
 
+// context.cpp (capi_internal.hpp): the schedule rule of a layered-only code
+namespace kml_host {
+int schedule_refusal(kml_ctx *c, const char *who);
+}
+
 extern "C" int kml_sim_point(kml_ctx *ctx, const kml_point_cfg *cfg, uint64_t seed, kml_allreduce_fn reduce,
                              void *ruser, kml_report_fn report, void *puser, uint64_t *counters) {
   if (!ctx || !cfg) return KML_E_ARG;
+  // refused before the first batch is generated: nothing is launched
+  if (int rc = kml_host::schedule_refusal(ctx, "kml_sim_point")) return rc;
   int64_t n[10];
   int rc = kml_run_config(ctx, nullptr, n);
   if (rc != KML_OK) return rc;
