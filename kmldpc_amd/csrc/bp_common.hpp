@@ -82,9 +82,16 @@ __device__ __forceinline__ double rcp_refine(double s) {
 // backward step, whose t is the normalised forward state itself (beta = 1).  With u = 1 - s (exact),
 // 1/s = 1 + u + u^2 + ..., which rounds to 1 + u, except that when 1 + u is a
 // midpoint (s < 1 an odd multiple of 2^-53 below 1) the positive u^2 term
-// rounds it up; 1 + (u + 2^-80) reproduces both (u + 2^-80 is exact, and
-// 2^-80 breaks exactly the ties u^2 breaks).  So rcp_near1(s) = RN(1/s): two
-// instructions instead of a quarter-rate v_rcp_f64 and four fmas.  With a correctly
+// rounds it up; RN(1 + u + b) reproduces both for any bias b in (0, 2^-54): u is
+// a multiple of 2^-53 in the domain (and 1 + u a double when s > 1, where the
+// result's grid is 2^-53), so b moves no value across a midpoint and breaks
+// exactly the ties u^2 breaks.  So rcp_near1(s) = RN(1/s) in one
+// instruction instead of a quarter-rate v_rcp_f64 and four fmas: X2 * Y =
+// 2 + 2^-77 exactly (X2 = 2 (1 + 2^-26), Y = 1 - 2^-26 + 2^-52: (1 + a)(1 - a +
+// a^2) = 1 + a^3), so fma(X2, Y, -s) forms 2 + 2^-77 - s = 1 + u + 2^-77 exactly
+// and rounds once; -s is a source modifier (v_fma_f64 r, X2, Y, -s), and 1 - s is
+// never formed (tests/test_rcp_near1_model.py checks all 12,289 s in exact
+// rationals).  With a correctly
 // rounded reciprocal the division tail (m = RN(n r), q = fma(fma(-s, m, n), r,
 // m)) is off only when n / s lies within 2^-51 ulp of a rounding midpoint;
 // tools/verify_cn_division.py enumerates every such n for |s - 1| <= 64 ulp
@@ -92,10 +99,7 @@ __device__ __forceinline__ double rcp_refine(double s) {
 // refinement is NOT RN(1/s) on six of these s (s = 1 - k 2^-53, k = 3, 5, ...,
 // 13: one ulp low), and hipcc's '/' then misrounds three significands (the
 // GPU test test_cn_reciprocal_exhaustive shows both).
-// Two instructions: X * Y = 1 + 2^-78 exactly (X = 1 + 2^-26, Y = 1 - 2^-26 +
-// 2^-52), so fma(X, Y, 1 - s) is RN(1 + u + 2^-78) with one rounding — the
-// same tie-breaking as 1 + (u + 2^-80) without the third add.
-__device__ __forceinline__ double rcp_near1(double s) { return fma(0x1.0000004p+0, 0x1.ffffff8000002p-1, 1.0 - s); }
+__device__ __forceinline__ double rcp_near1(double s) { return fma(0x1.0000004p+1, 0x1.ffffff8000002p-1, -s); }
 
 // Reciprocals of the R sums of one CN step (R independent rows): the near-one
 // formula, without a check that the sums are in its range (|s - 1| <= 2^-40).

@@ -1,7 +1,9 @@
 """Exact check of the CN phases' division n / s for sums s near 1.
 
 The CN kernels form q = fma(fma(-s, m, n), r, m), m = RN(n * r), with r the
-near-one reciprocal rcp_near1(s) = RN(1/s) (bp_common.hpp).  On the GPU,
+near-one reciprocal rcp_near1(s) = fma(X2, Y, -s) (bp_common.hpp: X2 Y =
+2 + 2^-77 exactly, one rounding), modelled here as the exact product minus s
+rounded once and checked against RN(1/s) on every s used.  On the GPU,
 rcp_near1 equals hipcc's refined reciprocal for every s with |s - 1| <= 2^-40
 except s = 1 - k 2^-53, k in {3, 5, ..., 13} (tests/test_gpu_parity.py
 test_cn_reciprocal_exhaustive measures it), where hipcc's is one ulp lower.
@@ -23,10 +25,16 @@ from fractions import Fraction as F
 import sys
 
 TWO52, TWO53 = 2 ** 52, 2 ** 53
+X2, Y = F(float.fromhex("0x1.0000004p+1")), F(float.fromhex("0x1.ffffff8000002p-1"))  # bp_common.hpp rcp_near1
 
 
 def rn(x):
     return F(float(x))  # CPython: Fraction -> float is correctly rounded
+
+
+def rcp_near1(s):
+    """fma(X2, Y, -s): the exact product minus s, one rounding."""
+    return rn(X2 * Y - s)
 
 
 def tail(n, s, r):
@@ -59,11 +67,15 @@ def candidates(K, width):
 
 
 def main():
+    assert X2 * Y == 2 + F(1, 2 ** 77)
     bad = 0
     checked = 0
     cases = [(F(1) - F(k, TWO53), k) for k in range(1, 65)] + [(F(1) + F(j, TWO52), -j) for j in range(1, 65)]
     for s, k in cases:
-        r_rn = rn(1 / s)
+        r_rn = rcp_near1(s)
+        if r_rn != rn(1 / s):
+            bad += 1
+            print(f"near-one reciprocal is not RN(1/s): s = 1{'-' if k > 0 else '+'}{abs(k)} ulp")
         rs = [r_rn]
         if 3 <= k <= 13 and k % 2:
             rs.append(r_rn - F(1, TWO52))  # hipcc's refinement on these s
