@@ -111,6 +111,26 @@ constexpr int kCnAgePrio = 5;
 // swaps.  The phase still counts as run (iter, CNT_CN_PHASES).  Measured alone,
 // same box: 9.02 -> 8.93 ms per step (-1.0%); with the closed-form iteration
 // 0: 8.58 ms (-4.9%).
+//
+// The budget's last VN phase (SYN = false): that parity check reads only the
+// decision bit, the sign of the high word of each slot's q1, so of the last
+// iteration's VN phase only the forward chain and hard_decision are live: the
+// backward pass of a column (three proven pair-divisions, the near-one one and
+// three 16-byte stores) writes messages nobody reads.  The last iteration is
+// peeled out of the loop (decode_reg, below the loop: the loop holds the
+// generic iteration alone, and the peeled column code cannot disturb its
+// register allocation): per column the generic forward chain as it stands
+// (the same div2 calls, the same rerun when a quotient is unproven, the same
+// hard_decision), the decision byte, and hb << 31 into the +12 word of each
+// of the column's slots; then the barrier, the nine sign words read together
+// and the same vote.  No numerical argument is needed: the decisions are the
+// generic chain's own.  With a budget of 1 the peeled iteration is iteration
+// 0 and takes the closed form's decision on the FAST path.  The redo decision
+// is the loop's: sus is raised only by a forced redo (sus0) -- div2 sets a
+// flag only in its DEFER form, whose flag is the column's `bad` (the column
+// is rerun, settling each quotient), and the backward pass's unit-beta step
+// and hard_decision call forms that settle or need no proof -- so dropping
+// the backward pass drops no redo, and CNT_REDONE is the parent's.
 constexpr int kRegMaxKw = 64;  // K <= N <= 2304 (bp_regular_threads): 36 words
 #if KML_STAMPS
 __device__ unsigned long long kml_reg_stamps[8];
@@ -155,6 +175,27 @@ __device__ __forceinline__ double with_sign(double x, int bit) {
   return __hiloint2double((__double2hiint(x) & 0x7FFFFFFF) | (bit << 31), __double2loint(x));
 }
 
+// PROF: CntErr of one iteration's decisions (the epilogue's, word for word),
+// added into *perr; run by every wave between the VN phase's closing barrier
+// and the CN phase's vote.
+template <int T>
+__device__ __forceinline__ void prof_count(const DevCode &c, const unsigned char *cch, const unsigned short *ipos,
+                                           const uint64_t *refw, int *perr) {
+  const int lane = threadIdx.x & 63;
+  int errs = 0;
+  for (int w0 = threadIdx.x >> 6; w0 < c.Kw; w0 += 2 * (T / 64)) {
+    const int w1 = w0 + T / 64;
+    const uint64_t r0 = refw[w0];
+    const uint64_t r1 = w1 < c.Kw ? refw[w1] : 0ull;
+    const int i0 = w0 * 64 + lane, i1 = w1 * 64 + lane;
+    const int b0 = i0 < c.K ? cch[ipos[i0]] : 0;
+    const int b1 = i1 < c.K && w1 < c.Kw ? cch[ipos[i1]] : 0;
+    const uint64_t m0 = __ballot(b0), m1 = __ballot(b1);
+    errs += __popcll(m0 ^ r0) + (w1 < c.Kw ? __popcll(m1 ^ r1) : 0);
+  }
+  if (lane == 0 && errs) atomicAdd(perr, errs);
+}
+
 // Returns true when a FAST decode met a quotient dd_check could not prove
 // correctly rounded (exact_div.hpp): the caller redoes the codeword with
 // FAST = false.  The decision is taken at the CN phase's closing barrier,
@@ -186,7 +227,9 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
 #if KML_STAMPS
   unsigned long long ws_acc[4] = {0, 0, 0, 0}, ws_prev = __builtin_amdgcn_s_memtime();
 #endif
-  for (; iter < a.iter_count; ++iter) {
+  // SYN == false: the budget's last iteration is peeled (below the loop)
+  const int loop_end = SYN ? a.iter_count : a.iter_count - 1;
+  for (; iter < loop_end; ++iter) {
     // Wave priorities (s_setprio) fall as a wave advances through a phase, so
     // the SIMD arbiter (priority, then age) favours the waves that are behind:
     // the 3 waves of a SIMD reach the barrier together instead of the oldest
@@ -278,21 +321,7 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     REG_WSTAMP(0);
     __syncthreads();
     REG_WSTAMP(1);
-    if constexpr (PROF) {  // CntErr of iteration iter's decisions (the epilogue's, word for word)
-      const int lane = threadIdx.x & 63;
-      int errs = 0;
-      for (int w0 = threadIdx.x >> 6; w0 < c.Kw; w0 += 2 * (T / 64)) {
-        const int w1 = w0 + T / 64;
-        const uint64_t r0 = refw[w0];
-        const uint64_t r1 = w1 < c.Kw ? refw[w1] : 0ull;
-        const int i0 = w0 * 64 + lane, i1 = w1 * 64 + lane;
-        const int b0 = i0 < c.K ? cch[ipos[i0]] : 0;
-        const int b1 = i1 < c.K && w1 < c.Kw ? cch[ipos[i1]] : 0;
-        const uint64_t m0 = __ballot(b0), m1 = __ballot(b1);
-        errs += __popcll(m0 ^ r0) + (w1 < c.Kw ? __popcll(m1 ^ r1) : 0);
-      }
-      if (lane == 0 && errs) atomicAdd(&perr[iter], errs);
-    }
+    if constexpr (PROF) prof_count<T>(c, cch, ipos, refw, &perr[iter]);
 
     // The early-stop parity check rides on the CN phase: in steps 0..H-1 the
     // even lane loads the row's edges [0, H) and the odd lane [H, DC), whose
@@ -311,16 +340,7 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
     // issued before the c2v STOREs (the partner's store of this step hits the
     // slot the lane is about to read), and LDS executes a wave's operations in
     // program order.
-    if (!SYN && iter + 1 == a.iter_count) {
-      // the budget's last CN phase without syndrome output: only the parity
-      // check is read (argument above: "Without syndrome output")
-#pragma unroll
-      for (int r = 0; r < RC; ++r) {
-        par[r] = 0;
-#pragma unroll
-        for (int st = 0; st < H; ++st) par[r] ^= lds_ld<unsigned>(rb[r] + st * 32 + 12);
-      }
-    } else {
+    {  // (the budget's last CN phase without syndrome output is below the loop)
       double x0[RC][H], x1[RC][H];  // lower-half chain states, kept for the swap
       double s0[RC], s1[RC];        // current chain state
 #pragma unroll
@@ -410,6 +430,113 @@ __device__ __forceinline__ bool decode_reg(const DevCode &c, const BpLaunch &a, 
 #pragma unroll
       for (int r = 0; r < RC; ++r)
         if (!odd) a.syn[(long long)cw * c.M + crow[r]] = syn0[r];  // alpha past the last edge (:274)
+    }
+  }
+  // The budget's last iteration without syndrome output, peeled (argument in
+  // the header: "The budget's last VN phase"): below the loop, so that its
+  // column code is not merged with the loop's.
+  if constexpr (!SYN) {
+    if (!conv && iter + 1 == a.iter_count) {
+#if KML_STAMPS
+      unsigned long long hot_acc[4];
+      for (int i = 0; i < 4; ++i) {
+        hot_acc[i] = ws_acc[i];
+        ws_acc[i] = 0;
+      }
+#endif
+      __builtin_amdgcn_s_setprio(3);
+      int hbs[RV];
+      if (FAST && iter == 0) {  // budget 1: the closed form's decisions
+#pragma unroll
+        for (int r = 0; r < RV; ++r) {
+          double p = pv[r];
+          asm volatile("" : "+v"(p));
+          hbs[r] = p > 1.0 - p ? 0 : 1;
+        }
+      } else {
+        double c0s[RV][DV];
+#pragma unroll
+        for (int r = 0; r < RV; ++r)
+#pragma unroll
+          for (int k = 0; k < DV; ++k) c0s[r][k] = iter == 0 ? 0.5 : lds_ld<double>(vaddr[r][k]);
+        // The generic column's forward chain, as it stands in the loop.  It
+        // is one dependent sequence per column (the loop's column overlaps it
+        // with its backward chains), so the RV columns' deferring chains run
+        // as one straight-line block that the scheduler interleaves; then the
+        // rare reruns, then the decisions.
+        double n0[RV], n1[RV];
+        bool bad[RV];
+        auto head = [&](int r, auto defer) {
+          constexpr bool D = FAST && decltype(defer)::value;
+          bad[r] = false;
+          double a0 = pv[r], a1 = 1.0 - pv[r];
+#pragma unroll
+          for (int k = 0; k < DV; ++k) {
+            const double c0 = c0s[r][k];
+            n0[r] = a0 * c0;
+            n1[r] = a1 * (1.0 - c0);
+            if (k + 1 < DV) div2<FAST, false, D>(n0[r], n1[r], n0[r] + n1[r], a0, a1, bad[r]);
+          }
+        };
+#pragma unroll
+        for (int r = 0; r < RV; ++r) head(r, std::true_type{});
+#pragma unroll
+        for (int r = 0; r < RV; ++r)
+          if (bad[r]) head(r, std::false_type{});
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int r = 0; r < RV; ++r) hbs[r] = hard_decision<FAST>(n0[r], n1[r], sus);  // the posterior's only use
+      }
+      // the decision byte, and the decision bit where the parity check below
+      // reads it: the high word of each of the column's slots
+#pragma unroll
+      for (int r = 0; r < RV; ++r) {
+        lds_st<unsigned char>(hd + r * T, (unsigned char)hbs[r]);
+#pragma unroll
+        for (int k = 0; k < DV; ++k) lds_st<unsigned>((vaddr[r][k] & ~15u) + 12, (unsigned)hbs[r] << 31);
+      }
+      __builtin_amdgcn_s_setprio(0);
+      REG_WSTAMP(0);
+      __syncthreads();
+      REG_WSTAMP(1);
+      if constexpr (PROF) prof_count<T>(c, cch, ipos, refw, &perr[iter]);
+      // the parity check alone (argument above: "Without syndrome output"):
+      // the pair's RC * H sign words, loaded together
+      unsigned sw[RC][H];
+#pragma unroll
+      for (int r = 0; r < RC; ++r)
+#pragma unroll
+        for (int st = 0; st < H; ++st) sw[r][st] = lds_ld<unsigned>(rb[r] + st * 32 + 12);
+      unsigned pw = 0;
+#pragma unroll
+      for (int r = 0; r < RC; ++r) {
+        unsigned x = sw[r][0];
+#pragma unroll
+        for (int st = 1; st < H; ++st) x ^= sw[r][st];
+        pw = r == 0 ? x >> 31 : __builtin_amdgcn_alignbit(pw, x, 31);
+      }
+      const bool fail = pw != (unsigned)swap_pair_i((int)pw);
+      REG_WSTAMP(2);
+      const int wg = FAST ? wg_any2<T / 64>(fail, sus, wflags) : wg_any<T / 64>(fail, wflags);
+      REG_WSTAMP(3);
+#if KML_STAMPS
+      if ((threadIdx.x & 63) == 0) {  // the peeled iteration: rows 12..14 by wave group, [15][0] its count
+        for (int i = 0; i < 4; ++i) {
+          atomicAdd(&kml_reg_wave_stamps[12 + (threadIdx.x >> 8)][i], ws_acc[i]);
+          ws_acc[i] = hot_acc[i];
+        }
+        if (threadIdx.x == 0) atomicAdd(&kml_reg_wave_stamps[15][0], 1ull);
+      }
+#endif
+      if (FAST && (wg & 2)) {  // sus: a forced redo (sus0) alone, as in the loop (header: "The redo decision")
+        iter_out = iter;
+        conv_out = false;
+        return true;
+      }
+      if (wg & 1)
+        ++iter;  // the phase counts as run
+      else
+        conv = true;
     }
   }
 #if KML_STAMPS

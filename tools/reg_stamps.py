@@ -47,9 +47,19 @@ def main():
     for i, n in enumerate(NAMES):
         print(f"  {n:24s} {st[i] / ncw:9.0f} cycles/cw  {100 * st[i] / ncw / tot:5.1f}%")
     print(f"  {'total':24s} {tot:9.0f} cycles/cw; iterations {st[3] / max(its, 1):.0f} cycles per CN phase")
-    print("  per wave, cycles per CN phase: VN compute, VN barrier, CN compute, CN barrier")
+    # the budget's peeled last iteration (SYN = false) is stamped apart: rows 12..14 hold its
+    # sums by wave group, [15][0] its count; rows 0..11 then cover the loop's iterations alone
+    npeel = ws[15][0]
+    hot = max(its - npeel, 1)
+    print(f"  per wave, cycles per CN phase of the loop ({hot / ncw:.2f} per codeword): "
+          "VN compute, VN barrier, CN compute, CN barrier")
     for w in range(12):
-        print(f"    wave {w:2d}: " + " ".join(f"{x / max(its, 1):7.0f}" for x in ws[w]))
+        print(f"    wave {w:2d}: " + " ".join(f"{x / hot:7.0f}" for x in ws[w]))
+    if npeel:
+        print(f"  peeled last iteration ({npeel / ncw:.2f} per codeword), cycles per wave and phase: "
+              "VN (forward chain), VN barrier, parity reads, CN barrier")
+        for g in range(3):
+            print(f"    waves {4 * g:2d}-{4 * g + 3:2d}: " + " ".join(f"{x / (4 * npeel):7.0f}" for x in ws[12 + g]))
 
 
 if __name__ == "__main__":
